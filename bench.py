@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Throughput benchmark of the MI355X contrastive training step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -24,11 +24,18 @@ trainer_unfreeze.py:1064-1117).  --global-batch G overrides (e.g. 256 at N=1 = 4
 --gpus N without torchrun: N ranks are spawned here (before anything touches the GPU), one per
 GPU, rendezvous on 127.0.0.1.  Under torchrun WORLD_SIZE must equal N.
 
-Rank 0 prints one JSON line.  `roofline` is for the dominant kernel (the bf16 GEMM
-instantiation with the largest share of step time), timed per launch with HIP events on the
-launch stream during the timed steps; `hbm_kernels` gives the achieved HBM GB/s of the fbank and
-LayerNorm launches (same method); `cpu_baseline` times the oracle (CPU fp32 restatement of the
-same step, oracle/) on the host at N=1, BASELINE.md §3 protocol.
+Rank 0 prints one JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline figures (`value`, `ms_per_step`, ...); `roofline`, `hbm_kernels` and `cpu_baseline` are
+null.  --full measures them too, after the timed steps: `roofline` is for the dominant kernel (the
+bf16 GEMM instantiation with the largest share of step time), timed per launch with HIP events on
+the launch stream during --trace-steps extra steps; `hbm_kernels` gives the achieved HBM GB/s of
+the fbank and LayerNorm launches (same method); `cpu_baseline` times the oracle (CPU fp32
+restatement of the same step, oracle/) on the host at N=1, BASELINE.md §3 protocol.
+
+--dump-outputs DIR: rank 0 writes what the last timed step computed as DIR/<name>.npy (float32):
+loss, s_pos, s_neg and, for a train step, a fixed seeded sample of the updated parameters and of
+their gradients (params_sample, grads_sample).  Inputs, initial weights and the dropout seeds are
+seeded, so two runs with the same arguments compute the same arrays.
 """
 from __future__ import annotations
 
@@ -84,7 +91,12 @@ def parse(argv=None):
     ap.add_argument("--trace-steps", type=int, default=2,
                     help="extra (untimed) steps whose launches are timed with HIP events for roofline / hbm_kernels "
                          "(at least 1: the roofline object needs them)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what takes runs of its own: the traced steps behind "
+                         "`roofline` / `hbm_kernels` and, at N=1, the CPU baseline (a plain run reports them as null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-batch", type=int, default=4, help="BASELINE.md §3: B=4")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU steps (median), after 2 warm-ups")
     args = ap.parse_args(argv)
@@ -255,6 +267,74 @@ def hbm_traffic(kernel, c5=False):
     return d[kernel]["hbm_bytes_per_launch"], os.path.relpath(files[-1], ROOT)
 
 
+def traced_figures(args, step, own, trace, htrace, c5):
+    """--full: (roofline, hbm_kernels) from the per-launch HIP event timings of the traced steps.
+    own: the step's stream.  Launches on it only: a side-stream launch (the text encoder) overlaps
+    the main stream, so its event interval includes time spent waiting for CUs."""
+    agg = {}
+    for name, flops, e0, e1, _shape, sid in trace:
+        if sid != own:
+            continue
+        a = agg.setdefault(name, [0, 0.0, 0.0])
+        a[0] += 1
+        a[1] += flops
+        a[2] += e0.elapsed_time(e1) * 1e-3
+    if not agg:
+        raise SystemExit("bench: no GEMM launch was traced on the step's stream (--trace-steps must be >= 1)")
+    dom = max(agg, key=lambda k: agg[k][2])
+    n_l, fl, tm = agg[dom]
+    achieved = fl / tm / 1e12
+    gemm_time = sum(a[2] for a in agg.values()) / args.trace_steps
+    hagg = {}
+    # the optimizer's launches (Σg², AdamW) on its own stream with overlap_optimizer: they share
+    # the chip with the next step's forward, so their event intervals are in-step times
+    opt_sid = step._opt_stream.cuda_stream if getattr(step, "_opt_stream", None) is not None else None
+    for name, nb, e0, e1, sid in htrace:
+        if sid != own and not (sid == opt_sid and name in ("adamw", "sumsq")):
+            continue
+        a = hagg.setdefault(name, [0, 0.0, 0.0])
+        a[0] += 1
+        a[1] += nb
+        a[2] += e0.elapsed_time(e1) * 1e-3
+    hbm = {k: {"launches_per_step": n // args.trace_steps, "avg_launch_us": round(t_ / n * 1e6, 2),
+               "algorithmic_mb_per_launch": round(b / n / 1e6, 3), "achieved_GBps": round(b / t_ / 1e9, 1),
+               "frac_of_8TBps": round(b / t_ / 1e9 / HBM_PEAK_GBPS, 4), "ms_per_step": round(t_ / args.trace_steps * 1e3, 3)}
+           for k, (n, b, t_) in sorted(hagg.items())}
+    peak = FP8_PEAK_TFLOPS if dom in ("gemm_mx8_kernel", "gemm_8ph_kernel<mx8>") else BF16_PEAK_TFLOPS
+    traffic, traffic_src = hbm_traffic(dom, c5=c5)
+    roofline = {"bound": "mfma", "kernel": dom, "launches_per_step": n_l // args.trace_steps,
+                "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
+                "frac": round(achieved / peak, 4), "traffic": traffic,
+                "traffic_unit": "HBM bytes per launch", "traffic_source": traffic_src,
+                "avg_launch_us": round(tm / n_l * 1e6, 2), "algorithmic_gflop_per_launch": round(fl / n_l / 1e9, 3),
+                "gemm_ms_per_step_all_variants": round(gemm_time * 1e3, 2),
+                "timing": f"HIP events per launch on the launch stream, {args.trace_steps} traced steps after the timed ones; main-stream launches only"}
+    return roofline, hbm
+
+
+DUMP_SAMPLE = 1 << 20   # entries of the flat parameter / gradient buffers written by --dump-outputs
+
+
+def dump_outputs(path, step, model, evaluation):
+    """--dump-outputs: what the last timed step gave its caller, as float32 <name>.npy under `path`:
+    the loss and the per-pair similarities (TrainStep.last / EvalStep's return) and, for a train
+    step, the state it left behind: the same seeded DUMP_SAMPLE entries of the trained fp32
+    parameters after AdamW and of their (all-reduced) gradients, 4 MiB each."""
+    import numpy as np
+    import torch
+    step.sync()
+    arrays = dict(step.last)
+    if not evaluation:
+        st = model.store
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, st.n_grad, (min(DUMP_SAMPLE, st.n_grad),), generator=g).sort().values.to(st.device)
+        arrays["params_sample"] = st.master[idx]
+        arrays["grads_sample"] = st.grad[idx]
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 # ---------------------------------------------------------------------- launcher
 def _free_port():
     with socket.socket() as s:
@@ -309,6 +389,9 @@ def main(argv=None):
     if os.environ.get("STE_BENCH_SHARE_GPU") == "1":
         local = 0
     torch.cuda.set_device(local)
+    # the step draws its dropout and layerdrop seeds from torch's default generator: seeded per rank,
+    # so that the same arguments give the same run (--dump-outputs compares builds output for output)
+    torch.manual_seed(rank)
     if world > 1:
         backend = os.environ.get("STE_BENCH_BACKEND", "nccl")
         if backend == "nccl":
@@ -370,55 +453,25 @@ def main(argv=None):
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-        # per-launch HIP-event timings (roofline, hbm_kernels) on extra steps of the same
+        loss = float(step.last["loss"].item())
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, step, model, args.eval)
+        # --full: per-launch HIP-event timings (roofline, hbm_kernels) on extra steps of the same
         # workload after the timed ones: the ~1,200 event records per step slow the host's
         # enqueue, which keeps pace with the GPU only just (profiles/graph_probe.py), so they
         # stay out of the timed region
-        ops.GEMM_TRACE, ops.HBM_TRACE = [], []
-        for _ in range(args.trace_steps):
-            run()
-        torch.cuda.synchronize()
+        if args.full:
+            ops.GEMM_TRACE, ops.HBM_TRACE = [], []
+            for _ in range(args.trace_steps):
+                run()
+            torch.cuda.synchronize()
     trace, ops.GEMM_TRACE = ops.GEMM_TRACE, None
     htrace, ops.HBM_TRACE = ops.HBM_TRACE, None
-    loss = float(step.last["loss"].item())
     if world > 1:
         t = torch.tensor([elapsed], device=f"cuda:{local}", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # dominant-kernel roofline from per-launch HIP event timings of the timed steps
-    # launches on the step's own stream only: a side-stream launch (the text encoder) overlaps the
-    # main stream, so its event interval includes time spent waiting for CUs
-    own = main_stream.cuda_stream
-    agg = {}
-    for name, flops, e0, e1, _shape, sid in trace:
-        if sid != own:
-            continue
-        a = agg.setdefault(name, [0, 0.0, 0.0])
-        a[0] += 1
-        a[1] += flops
-        a[2] += e0.elapsed_time(e1) * 1e-3
-    if not agg:
-        raise SystemExit("bench: no GEMM launch was traced on the step's stream (--trace-steps must be >= 1)")
-    dom = max(agg, key=lambda k: agg[k][2])
-    n_l, fl, tm = agg[dom]
-    achieved = fl / tm / 1e12
-    gemm_time = sum(a[2] for a in agg.values()) / args.trace_steps
-    hagg = {}
-    # the optimizer's launches (Σg², AdamW) on its own stream with overlap_optimizer: they share
-    # the chip with the next step's forward, so their event intervals are in-step times
-    opt_sid = step._opt_stream.cuda_stream if getattr(step, "_opt_stream", None) is not None else None
-    for name, nb, e0, e1, sid in htrace:
-        if sid != own and not (sid == opt_sid and name in ("adamw", "sumsq")):
-            continue
-        a = hagg.setdefault(name, [0, 0.0, 0.0])
-        a[0] += 1
-        a[1] += nb
-        a[2] += e0.elapsed_time(e1) * 1e-3
-    hbm = {k: {"launches_per_step": n // args.trace_steps, "avg_launch_us": round(t_ / n * 1e6, 2),
-               "algorithmic_mb_per_launch": round(b / n / 1e6, 3), "achieved_GBps": round(b / t_ / 1e9, 1),
-               "frac_of_8TBps": round(b / t_ / 1e9 / HBM_PEAK_GBPS, 4), "ms_per_step": round(t_ / args.trace_steps * 1e3, 3)}
-           for k, (n, b, t_) in sorted(hagg.items())}
     pairs = glob * args.steps / elapsed
     # SURVEY §8(d) algorithmic FLOPs per pair exist for the 10 s / 64-token configs c2/c3 (3
     # unfrozen layers) and c4 (5 + alignment head); other shapes report no step fraction
@@ -440,8 +493,9 @@ def main(argv=None):
                  "c5-shape (MX-fp8 Conformer fwd GEMMs)")
     else:
         cname = "custom"
-    peak = FP8_PEAK_TFLOPS if dom in ("gemm_mx8_kernel", "gemm_8ph_kernel<mx8>") else BF16_PEAK_TFLOPS
-    traffic, traffic_src = hbm_traffic(dom, c5=c5)
+    roofline = hbm = None
+    if args.full:
+        roofline, hbm = traced_figures(args, step, main_stream.cuda_stream, trace, htrace, c5)
     out = {
         "metric": ("evaluated audio–text pairs/sec, forward only (whole node), 10s@16kHz + 64-tok" if args.eval else
                    "audio–text pairs/sec (whole node), 10s@16kHz + 64-tok, 1/2/4/8 MI355X"),
@@ -468,17 +522,11 @@ def main(argv=None):
         **({"step_roofline_frac_fp8_peak": round(pairs * gflop / (world * FP8_PEAK_TFLOPS * 1e3), 4)}
            if (gflop and c5 and args.fp8) else {}),
         "gflop_per_pair": gflop,
-        "roofline": {"bound": "mfma", "kernel": dom, "launches_per_step": n_l // args.trace_steps,
-                     "achieved": round(achieved, 1), "peak": peak, "unit": "TFLOP/s",
-                     "frac": round(achieved / peak, 4), "traffic": traffic,
-                     "traffic_unit": "HBM bytes per launch", "traffic_source": traffic_src,
-                     "avg_launch_us": round(tm / n_l * 1e6, 2), "algorithmic_gflop_per_launch": round(fl / n_l / 1e9, 3),
-                     "gemm_ms_per_step_all_variants": round(gemm_time * 1e3, 2),
-                     "timing": f"HIP events per launch on the launch stream, {args.trace_steps} traced steps after the timed ones; main-stream launches only"},
+        "roofline": roofline,
         "hbm_kernels": hbm,
         "loss": round(loss, 5),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not raw:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not raw:
         out["cpu_baseline"] = cpu_baseline(args)
     elif rank == 0:
         out["cpu_baseline"] = None

@@ -16,7 +16,7 @@ TAG=${1:?tag}
 shift
 OUT=gpurun_out/prof_$TAG
 mkdir -p "$OUT"
-BENCH=(python3 bench.py --steps 5 --warmup 3 --no-cpu-baseline "$@")
+BENCH=(python3 bench.py --full --steps 5 --warmup 3 --no-cpu-baseline "$@")
 echo "[profile] kernel trace: ${BENCH[*]}"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/trace" -o run -- "${BENCH[@]}" \
     > "$OUT/bench_under_trace.json"

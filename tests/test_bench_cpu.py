@@ -45,6 +45,57 @@ def test_plan_c3_eight_ranks_and_overrides():
         b.batch_plan(b.parse(["--global-batch", "100"]), 8)
 
 
+def _bench_module():
+    from importlib import util
+    spec = util.spec_from_file_location("bench_mod", ROOT / "bench.py")
+    b = util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_full_and_dump_outputs_are_off_by_default():
+    b = _bench_module()
+    a = b.parse(["--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (3, 1)
+    a = b.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float32_arrays_and_a_fixed_sample(tmp_path):
+    """--dump-outputs: every array of the step's `last` dict plus the same seeded sample of the flat
+    parameter and gradient buffers on every call, as float32 .npy files."""
+    import types
+
+    import numpy as np
+    import torch
+    b = _bench_module()
+    n = 5000
+    store = types.SimpleNamespace(n_grad=n, device=torch.device("cpu"),
+                                  master=torch.arange(2 * n, dtype=torch.float32),
+                                  grad=-torch.arange(n, dtype=torch.float32))
+    model = types.SimpleNamespace(store=store)
+    synced = []
+    step = types.SimpleNamespace(sync=lambda: synced.append(1),
+                                 last={"loss": torch.tensor([0.5]), "s_pos": torch.ones(4, dtype=torch.float64),
+                                       "s_neg": torch.zeros(4)})
+    b.dump_outputs(str(tmp_path / "a"), step, model, False)
+    b.dump_outputs(str(tmp_path / "b"), step, model, False)
+    assert synced
+    names = {"loss", "s_pos", "s_neg", "params_sample", "grads_sample"}
+    assert {p.stem for p in (tmp_path / "a").glob("*.npy")} == names
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["loss"].tolist() == [0.5] and got["s_pos"].tolist() == [1.0] * 4
+    p, g = got["params_sample"], got["grads_sample"]
+    assert p.shape == g.shape == (min(b.DUMP_SAMPLE, n),)
+    assert (p < n).all() and np.array_equal(g, -p) and len(np.unique(p)) > n // 4   # trained entries, same indices
+    for k in names:
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy"))
+    # an evaluation step leaves no state behind: only what it returned
+    b.dump_outputs(str(tmp_path / "e"), step, model, True)
+    assert {p.stem for p in (tmp_path / "e").glob("*.npy")} == {"loss", "s_pos", "s_neg"}
+
+
 def test_world_size_must_match_gpus():
     env = dict(os.environ, STE_BENCH_PLAN_ONLY="1", WORLD_SIZE="2", RANK="0", LOCAL_RANK="0")
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "4"], capture_output=True, text=True,
