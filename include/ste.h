@@ -112,10 +112,10 @@ int ste_gemm_tile_map(int t, int num_m, int num_n, int* tm, int* tn);
 int ste_gemm_f32(const ste_gemm_args* args, void* stream);
 
 /* Which kernel ste_gemm would launch for these args (no launch, host-only):
- * STE_GEMM_KERNEL_SMALL/BIG/8PH + variant, variant = (a_kc ? 0 : 2) + (b_kc ? 0 : 1).
+ * STE_GEMM_KERNEL_SMALL (the 128x128 kernel), _8PH (the persistent 8-phase kernel) or _SPLITK
+ * (8-phase K-slabs and a reduction) + variant, variant = (a_kc ? 0 : 2) + (b_kc ? 0 : 1).
  * Lets profilers and bench.py attribute per-launch time to the rocprof kernel name. */
 #define STE_GEMM_KERNEL_SMALL 0
-#define STE_GEMM_KERNEL_BIG 4
 #define STE_GEMM_KERNEL_8PH 8
 #define STE_GEMM_KERNEL_SPLITK 12
 int ste_gemm_kernel(const ste_gemm_args* args);
@@ -144,7 +144,11 @@ int ste_gemm_mx8_kernel(const ste_gemm_args* args, int q_out);
  * default: about one wave of 256 CUs).  A value <= 0 leaves that threshold unchanged; the previous
  * values are returned through prev_bf16 / prev_mx8 (either may be NULL).  Parity tests lower them
  * so that a B <= 4 batch runs the same kernel instantiations as the b = 64 bench step; the planned
- * kernels accept any tile count (partial edge tiles take their guarded epilogue). */
+ * kernels accept any tile count (partial edge tiles take their guarded epilogue).
+ * Two limits.  The thresholds are atomics read once per ste_gemm / ste_gemm_mx8 call, when that
+ * call is planned: a graph captured earlier keeps the plan it was captured with, whatever is set
+ * afterwards.  And the call is meant for test set-up, before any capture, not for tuning a
+ * running step. */
 int ste_gemm_plan_min_tiles(int bf16_tiles, int mx8_tiles, int* prev_bf16, int* prev_mx8);
 /* bf16 x [rows][K] (row stride ldx) -> e4m3 q [rows][K] and E8M0 scales [rows][K/32]:
  * scale 2^e, e = ceil(log2(amax/448)) per 32-element block (no saturation; zero blocks 2^-127). */

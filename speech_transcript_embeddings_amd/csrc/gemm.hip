@@ -14,16 +14,23 @@
 // KM tiles are staged k-major in LDS and read with ds_read_b64_tr_b16 (hardware
 // transpose), so no operand is ever transposed in HBM.
 //
-// Two kernels, chosen per shape:
-//  * gemm_big: 256x256x64 tile, 512 threads (8 waves as 2(M)x4(N), 128x64 per wave,
-//    8x4 v_mfma_f32_16x16x32_bf16), operands streamed global->LDS with global_load_lds
-//    (16 B/lane, no VGPR staging) into a 2-deep LDS ring whose XOR swizzle is realised
-//    through the per-lane SOURCE address (the LDS image is lane-linear).  Used when the
-//    grid has >= ~1 wave of 256 CUs and K % 64 == 0 (all big encoder GEMMs).
+// The kernels, chosen per launch by one host-side plan (plan_gemm):
 //  * gemm_bf16_kernel: 128x128x64 tile, 256 threads, register-staged (zero-filled
-//    tails in every dimension): small / ragged GEMMs and the dW reductions.
-// Both: XCD-aware bijective block remap + grouped tile order for L2 reuse, and an
-// LDS-staged epilogue with row-contiguous (16 B/lane) loads and stores.
+//    tails in every dimension): small / ragged GEMMs and the K % 64 tails of the plans below.
+//  * gemm_8ph_kernel: persistent, 256x256x64 tile, 512 threads (8 waves as 2(M)x4(N),
+//    128x64 per wave, 8x4 v_mfma_f32_16x16x32_bf16), operands streamed global->LDS with
+//    global_load_lds (16 B/lane, no VGPR staging) in four half-tile phases per K-tile; the
+//    XOR swizzle is realised through the per-lane SOURCE address (the LDS image is
+//    lane-linear).  The epilogue is compile-time for the hot configurations (STE_EPI_SPECS),
+//    generic otherwise.  Used when the grid has >= ~1 wave of 256 CUs and K % 64 == 0 (all
+//    big encoder GEMMs), and for the K-slabs of the split plans.
+//  * splitk_reduce_kernel / splitk_epi_kernel: sum the fp32 K-slabs of a weight-gradient
+//    split (alpha/beta only) or of a few-tile split (full epilogue), in slab order.
+//  * MX-fp8 (ste_gemm_mx8): gemm_8ph_kernel<.., MX> on the same schedule, and the
+//    single-stage gemm_mx8_kernel for shapes and epilogues it is not planned for.
+// All GEMM kernels: XCD-aware bijective block remap + grouped tile order for L2 reuse, and
+// an LDS-staged epilogue with row-contiguous (16 B/lane) loads and stores.
+#include <atomic>
 #include <cstdio>
 #include <utility>
 #include "common.h"
@@ -745,126 +752,8 @@ __global__ __launch_bounds__(small::NT, 2) void gemm_bf16_kernel(ste_gemm_args p
     colsum_flush(p, csum, n0 + wn * 64, n0 + wn * 64 + 32, batch, lane, ((int64_t)batch * num_m + tm) * 2 + wm);
 }
 
-// ================================================================= big kernel
-namespace big {
-constexpr int BM = 256, BN = 256, BK = 64, NT = 512;
-constexpr int TILE_BYTES = BM * BK * 2;        // 32 KiB per operand per stage
-constexpr int STAGE_BYTES = 2 * TILE_BYTES;
-constexpr int LDS_BYTES = 2 * STAGE_BYTES;     // 128 KiB: 2-deep ring
-constexpr int EPI_ROWS = 32;                   // rows staged per epilogue pass per wave
-
-// issue this wave's 4 global_load_lds pieces (1 KiB each) of one operand tile.
-// KC tile [256 rows][64 k]: piece p = rows 8p..8p+7; lane L -> row 8p+L/8, chunk (L%8)^(L/8).
-// KM tile [64 k][256 rows] (512 B k-rows): piece p = k-rows 2p,2p+1; lane L -> k-row 2p+L/32,
-//   logical chunk (L%32) ^ km_xor(k-row).  Row indices past the operand are clamped (their
-//   products only reach discarded outputs); K % 64 == 0 is required.
-template <bool KC>
-STE_DEV void issue_tile(const bf16* base, int64_t ld, int row0, int rows, int k0, char* tile, int wave, int lane) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int piece = wave * 4 + i;
-    const bf16* src;
-    if (KC) {
-      const int r = piece * 8 + (lane >> 3);
-      const int ch = (lane & 7) ^ (lane >> 3);
-      const int gr = min(row0 + r, rows - 1);
-      src = base + (int64_t)gr * ld + k0 + ch * 8;
-    } else {
-      const int kk = piece * 2 + (lane >> 5);
-      const int ch = (lane & 31) ^ km_chunk_xor(kk);
-      const int gc = min(row0 + ch * 8, rows - 8);
-      src = base + (int64_t)(k0 + kk) * ld + gc;
-    }
-    __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)(tile + piece * 1024), 16, 0, 0);
-  }
-}
-}  // namespace big
-
-template <bool A_KC, bool B_KC>
-__global__ __launch_bounds__(big::NT, 2) void gemm_big_kernel(ste_gemm_args p) {
-  using namespace big;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
-  const int num_m = (p.M + BM - 1) / BM, num_n = (p.N + BN - 1) / BN;
-  int batch, tm, tn;
-  map_tile(gridDim.x, num_m, num_n, batch, tm, tn);
-  const int m0 = tm * BM, n0 = tn * BN;
-  const bf16* A = (const bf16*)p.A + (int64_t)batch * p.strideA;
-  const bf16* B = (const bf16*)p.B + (int64_t)batch * p.strideB;
-
-  f32x4 acc[8][4];
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = p.K / BK;
-  issue_tile<A_KC>(A, p.lda, m0, p.M, 0, smem, wave, lane);
-  issue_tile<B_KC>(B, p.ldb, n0, p.N, 0, smem + TILE_BYTES, wave, lane);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-
-  for (int kt = 0; kt < nk; ++kt) {
-    const int cur = kt & 1;
-    if (kt + 1 < nk) {
-      char* nxt = smem + (cur ^ 1) * STAGE_BYTES;
-      issue_tile<A_KC>(A, p.lda, m0, p.M, (kt + 1) * BK, nxt, wave, lane);
-      issue_tile<B_KC>(B, p.ldb, n0, p.N, (kt + 1) * BK, nxt + TILE_BYTES, wave, lane);
-    }
-    const char* ta = smem + cur * STAGE_BYTES;
-    const char* tb = ta + TILE_BYTES;
-#pragma unroll
-    for (int s = 0; s < 2; ++s) {
-      bf16x8 fb[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fb[j] = frag_load<B_KC, 512>(tb, wn * 64 + j * 16, s, lane);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const bf16x8 fa = frag_load<A_KC, 512>(ta, wm * 128 + i * 16, s, lane);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = mfma16(fa, fb[j], acc[i][j]);
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  }
-
-  // epilogue: 4 passes of 32 rows x 64 cols per wave through LDS
-  float* epi = reinterpret_cast<float*>(smem) + wave * EPI_ROWS * EPI_LD;
-  Csum csum = {};
-  // (explicit passes: a rolled pass loop would index acc dynamically and demote it to scratch)
-#define STE_EPI_PASS(PS)                                                                                     \
-  {                                                                                                          \
-    for (int ii = 0; ii < 2; ++ii) {                                                                         \
-      _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                        \
-        _Pragma("unroll") for (int r = 0; r < 4; ++r) {                                                      \
-          epi[(ii * 16 + (lane >> 4) * 4 + r) * EPI_LD + j * 16 + (lane & 15)] = acc[2 * (PS) + ii][j][r];   \
-        }                                                                                                    \
-      }                                                                                                      \
-    }                                                                                                        \
-    __builtin_amdgcn_s_waitcnt(0xc07f);                                                                      \
-    __builtin_amdgcn_wave_barrier();                                                                         \
-    for (int hh = 0; hh < big::EPI_ROWS; hh += 16) {                                                         \
-      if (!EPI_SKIP) epilogue_tile(p, epi + hh * EPI_LD, 16, m0 + wm * 128 + (PS) * big::EPI_ROWS + hh,     \
-                                   EPI_COL0, EPI_COL1, batch, lane, csum);                                   \
-    }                                                                                                        \
-    __builtin_amdgcn_s_waitcnt(0xc07f);                                                                      \
-    __builtin_amdgcn_wave_barrier();                                                                         \
-  }
-  constexpr bool EPI_SKIP = false;
-#define EPI_COL0 (n0 + wn * 64)
-#define EPI_COL1 (n0 + wn * 64 + 32)
-  STE_EPI_PASS(0) STE_EPI_PASS(1) STE_EPI_PASS(2) STE_EPI_PASS(3)
-#undef EPI_COL0
-#undef EPI_COL1
-  if (p.colsum)
-    colsum_flush(p, csum, n0 + wn * 64, n0 + wn * 64 + 32, batch, lane, ((int64_t)batch * num_m + tm) * 2 + wm);
-}
-
 // ============================================================ 8-phase kernel
-// Same 256x256x64 tile and 2(M)x4(N) waves as gemm_big, but each K-tile is split into
+// 256x256x64 tile, 8 waves as 2(M)x4(N) (128x64 per wave).  Each K-tile is split into
 // four half-tiles (A rows / B cols that one C-quadrant of every wave needs) and the
 // K-loop runs 4 phases per K-tile:
 //   phase 0: read B-half0 + A-half0 -> MFMA quadrant (A0,B0)     stage B-half1 of tile t+1
@@ -1485,7 +1374,6 @@ __global__ __launch_bounds__(ph8::NT, 1) void gemm_8ph_kernel(ste_gemm_args p, M
 #undef STAGE_PROLOGUE
 #undef STE_LDS_SYNC
 }
-#undef STE_EPI_PASS
 
 // CUs of the current device (one persistent workgroup each)
 int num_cus() {
@@ -1529,14 +1417,27 @@ int num_cus() {
   X(true, true, 0, STE_ACT_NONE)                             /* few-tile split-K slabs */ \
   X(false, false, 0, STE_ACT_NONE)                           /* dW split-K slabs   */
 
+// The one match of a launch against STE_EPI_SPECS, shared by the plan (and through it the
+// name query) and the launch: the entry's (flags, activation), or EF_GENERIC.
+struct EpiSpec {
+  int ef, act;
+};
+EpiSpec match_epi_spec(bool a_kc, bool b_kc, int ef, int act) {
+#define STE_MATCH(AK, BK, E, ACT) \
+  if (AK == a_kc && BK == b_kc && ef == (E) && act == (ACT)) return {(E), (ACT)};
+  STE_EPI_SPECS(STE_MATCH)
+#undef STE_MATCH
+  return {EF_GENERIC, 0};
+}
+
+// spec: the plan's match for these arguments; the X-macro only reaches its instantiation
 template <bool A_KC, bool B_KC>
-int launch_8ph(const ste_gemm_args& a, hipStream_t s) {
+int launch_8ph(const ste_gemm_args& a, EpiSpec spec, hipStream_t s) {
   const int nb = ((a.M + 255) / 256) * ((a.N + 255) / 256) * a.batch;
   const int grid = nb < num_cus() ? nb : num_cus();
-  const int ef = epi_flags(a);
 #define STE_TRY(AK, BK, E, ACT)                                                                       \
   if constexpr (AK == A_KC && BK == B_KC) {                                                           \
-    if (ef == (E) && a.act == (ACT)) {                                                                \
+    if (spec.ef == (E) && spec.act == (ACT)) {                                                        \
       hipLaunchKernelGGL((gemm_8ph_kernel<A_KC, B_KC, (E), (ACT)>), dim3(grid), dim3(ph8::NT),        \
                          ph8::LDS_BYTES, s, a, Mx8Args{});                                            \
       STE_CHECK_LAUNCH();                                                                             \
@@ -1545,6 +1446,7 @@ int launch_8ph(const ste_gemm_args& a, hipStream_t s) {
   }
   STE_EPI_SPECS(STE_TRY)
 #undef STE_TRY
+  if (spec.ef != EF_GENERIC) return STE_ERR_ARG;   // a spec of another operand layout: never planned
   hipLaunchKernelGGL((gemm_8ph_kernel<A_KC, B_KC, EF_GENERIC, 0>), dim3(grid), dim3(ph8::NT), ph8::LDS_BYTES, s, a,
                      Mx8Args{});
   STE_CHECK_LAUNCH();
@@ -1605,65 +1507,6 @@ __global__ __launch_bounds__(256) void splitk_epi_kernel(ste_gemm_args p, const 
   }
 }
 
-// Few-tile plan: k-contiguous operands, one output image, no column sums, N % 8 == 0, K a
-// multiple of 64 with >= 40 K-tiles (at 36 — the text QKV input gradient — the split only broke
-// even in isolation and its 2 x 25 MB of slabs still cost HBM time beside the audio stream), fewer 256x256 tiles than CUs / 2: S = 2
-// slabs (2 x tiles workgroups).  STE_GEMM_FEW_SPLIT=0 disables it (A/B).
-int few_split(const ste_gemm_args& a) {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = STE_AB_ENV("STE_GEMM_FEW_SPLIT");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!on || !a.a_kc || !a.b_kc || !a.ws || a.batch != 1 || a.colsum) return 0;
-  if ((a.N & 7) || (a.K & 63) || a.K / 64 < 40 || a.M < 2048) return 0;
-  const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
-  if (tiles * 2 > num_cus()) return 0;
-  if (2 * (int64_t)a.M * a.N * 4 > a.ws_bytes) return 0;
-  return 2;
-}
-
-// Batched weight gradients (both operands k-major, batch > 1: the wav2vec2 conv stack's per-clip
-// dW slabs over strided views, K = frames of one clip, usually ragged): the 8-phase kernel over
-// the whole-64 part of K (the batch fills the chip), the K % 64 tail accumulated by the small
-// kernel.  Plain alpha/beta epilogue only.
-bool batched_dw_ok(const ste_gemm_args& a) {
-  static int on = -1;   // STE_GEMM_BATCHED_DW=0: the small kernel (A/B)
-  if (on < 0) {
-    const char* e = STE_AB_ENV("STE_GEMM_BATCHED_DW");
-    on = (e && e[0] == '0') ? 0 : 1;
-  }
-  if (!on || a.a_kc || a.b_kc || a.batch < 2) return false;
-  if (a.bias || a.C2 || a.C3 || a.R || a.Z || a.colsum || a.row_scale || a.act || a.drop_p > 0.f) return false;
-  if ((a.M & 7) || (a.N & 7) || a.M < 256 || a.N < 256 || a.K < 1024) return false;
-  const long tiles = (long)((a.M + 255) / 256) * ((a.N + 255) / 256) * a.batch;
-  return tiles >= 240;
-}
-
-// Weight-gradient plan: S K-slabs of Kc (or Kc + 1: the K/64 - S·Kc leftover tiles, one each
-// to the first slabs) 64-deep tiles on the 8-phase kernel with both operands k-major; only a
-// ragged K % 64 tail goes to the small kernel.
-struct SplitPlan {
-  int S, Kc;  // S == 0: not applicable
-};
-SplitPlan splitk_plan(const ste_gemm_args& a) {
-  SplitPlan pl{0, 0};
-  if (a.a_kc || a.b_kc || !a.ws || a.batch != 1) return pl;
-  if (a.bias || a.C2 || a.C3 || a.R || a.Z || a.colsum || a.row_scale || a.act || a.drop_p > 0.f || a.c_bf16) return pl;
-  if ((a.M & 7) || (a.N & 7)) return pl;
-  const int nk = a.K / 64;
-  const int tiles = ((a.M + 255) / 256) * ((a.N + 255) / 256);
-  if (nk < 16 || tiles > 256) return pl;
-  int S = 256 / tiles;
-  if (S > nk / 8) S = nk / 8;
-  const int64_t slab = (int64_t)a.M * a.N * 4;
-  while (S > 1 && S * slab > a.ws_bytes) --S;
-  if (S < 1 || S * slab > a.ws_bytes) return pl;
-  pl.S = S;
-  pl.Kc = nk / S;
-  return pl;
-}
-
 template <bool A_KC, bool B_KC>
 int launch_small(const ste_gemm_args& a, hipStream_t s) {
   using namespace small;
@@ -1674,86 +1517,207 @@ int launch_small(const ste_gemm_args& a, hipStream_t s) {
   return 0;
 }
 
-template <bool A_KC, bool B_KC>
-int launch_big(const ste_gemm_args& a, hipStream_t s) {
-  using namespace big;
-  const int num_m = (a.M + BM - 1) / BM, num_n = (a.N + BN - 1) / BN;
-  const int nb = num_m * num_n * a.batch;
-  hipLaunchKernelGGL((gemm_big_kernel<A_KC, B_KC>), dim3(nb), dim3(NT), LDS_BYTES, s, a);
-  STE_CHECK_LAUNCH();
-  return 0;
+// ------------------------------------------------------------------ host-side plan
+// Which kernels a launch takes is decided once, in plan_gemm; ste_gemm, ste_gemm_kernel and
+// ste_gemm_kernel_name only read its result.  The A/B switches below read the environment in
+// -DSTE_AB builds only (STE_AB_ENV) and keep their defaults in the shipped library.
+bool env_is(const char* e, char c) { return e && e[0] == c; }
+
+// STE_GEMM_SMALL_ONLY=1: every shape on the 128x128 kernel, every MX GEMM single-stage (A/B)
+bool small_only() {
+  static const bool on = env_is(STE_AB_ENV("STE_GEMM_SMALL_ONLY"), '1');
+  return on;
 }
 
-bool big_ok_shape(const ste_gemm_args& a) {
-  if (a.K % big::BK) return false;
+// plan thresholds (ste_gemm_plan_min_tiles; the A/B build also reads STE_GEMM_MIN_TILES)
+std::atomic<int> g_min_tiles_bf16{-1}, g_min_tiles_mx8{240};
+int min_tiles_bf16() {
+  int v = g_min_tiles_bf16.load();
+  if (v < 0) {   // first use: the default, unless a concurrent ste_gemm_plan_min_tiles set one
+    const char* e = STE_AB_ENV("STE_GEMM_MIN_TILES");
+    const int dflt = e ? atoi(e) : 240;
+    if (g_min_tiles_bf16.compare_exchange_strong(v, dflt)) v = dflt;
+  }
+  return v;
+}
+
+int tiles_256(const ste_gemm_args& a) { return ((a.M + 255) / 256) * ((a.N + 255) / 256); }
+
+// what the 8-phase kernel's operand DMA needs: whole 64-deep K-tiles, A k-contiguous (or the
+// all-k-major weight-gradient plans below), 16-B chunks of a k-major B
+bool ph8_shape_ok(const ste_gemm_args& a) {
+  if (a.K % 64) return false;
   if (!a.a_kc || a.M < 8) return false;                 // dW reductions stay on the small kernel
   if (!a.b_kc && (a.N % 8)) return false;
   return true;
 }
-// plan thresholds (ste_gemm_plan_min_tiles; the A/B build also reads STE_GEMM_MIN_TILES)
-int g_min_tiles_bf16 = -1, g_min_tiles_mx8 = 240;
-int min_tiles_bf16() {
-  if (g_min_tiles_bf16 < 0) {
-    const char* e = STE_AB_ENV("STE_GEMM_MIN_TILES");
-    g_min_tiles_bf16 = e ? atoi(e) : 240;
-  }
-  return g_min_tiles_bf16;
+
+bool plain_epilogue(const ste_gemm_args& a) {   // alpha/beta only
+  return !(a.bias || a.C2 || a.C3 || a.R || a.Z || a.colsum || a.row_scale || a.act || a.drop_p > 0.f);
 }
-bool big_ok(const ste_gemm_args& a) {
-  if (!big_ok_shape(a)) return false;
-  const long tiles = (long)((a.M + 255) / 256) * ((a.N + 255) / 256) * a.batch;
-  return tiles >= min_tiles_bf16();
+
+// Few-tile plan: k-contiguous operands, one output image, no column sums, N % 8 == 0, K a
+// multiple of 64 with >= 40 K-tiles (at 36 — the text QKV input gradient — the split only broke
+// even in isolation and its 2 x 25 MB of slabs still cost HBM time beside the audio stream), fewer
+// 256x256 tiles than CUs / 2: S = 2 slabs (2 x tiles workgroups).  STE_GEMM_FEW_SPLIT=0 disables
+// it (A/B).
+int few_split_slabs(const ste_gemm_args& a) {
+  static const bool off = env_is(STE_AB_ENV("STE_GEMM_FEW_SPLIT"), '0');
+  if (off || !a.a_kc || !a.b_kc || !a.ws || a.batch != 1 || a.colsum || !ph8_shape_ok(a)) return 0;
+  if ((a.N & 7) || a.K / 64 < 40 || a.M < 2048) return 0;
+  if (tiles_256(a) * 2 > num_cus()) return 0;
+  if (2 * (int64_t)a.M * a.N * 4 > a.ws_bytes) return 0;
+  return 2;
+}
+
+// Batched weight gradients (both operands k-major, batch > 1: the wav2vec2 conv stack's per-clip
+// dW slabs over strided views, K = frames of one clip, usually ragged): the 8-phase kernel over
+// the whole-64 part of K (the batch fills the chip), the K % 64 tail accumulated by the small
+// kernel.  Plain alpha/beta epilogue only.  STE_GEMM_BATCHED_DW=0: the small kernel (A/B).
+bool batched_dw_ok(const ste_gemm_args& a) {
+  static const bool off = env_is(STE_AB_ENV("STE_GEMM_BATCHED_DW"), '0');
+  if (off || a.a_kc || a.b_kc || a.batch < 2 || !plain_epilogue(a)) return false;
+  if ((a.M & 7) || (a.N & 7) || a.M < 256 || a.N < 256 || a.K < 1024) return false;
+  return (long)tiles_256(a) * a.batch >= 240;
+}
+
+// Weight-gradient plan: S K-slabs of K/64/S (or one more: the leftover tiles, one each to the
+// first slabs) 64-deep tiles on the 8-phase kernel with both operands k-major, as many as fill
+// 256 CUs, leave >= 8 K-tiles per slab and fit the workspace; only a ragged K % 64 tail goes to
+// the small kernel.  0: not applicable.
+int dw_split_slabs(const ste_gemm_args& a) {
+  if (a.a_kc || a.b_kc || !a.ws || a.batch != 1 || !plain_epilogue(a) || a.c_bf16) return 0;
+  if ((a.M & 7) || (a.N & 7)) return 0;
+  const int nk = a.K / 64, tiles = tiles_256(a);
+  if (nk < 16 || tiles > 256) return 0;
+  int S = 256 / tiles;
+  if (S > nk / 8) S = nk / 8;
+  const int64_t slab = (int64_t)a.M * a.N * 4;
+  while (S > 1 && S * slab > a.ws_bytes) --S;
+  return (S < 1 || S * slab > a.ws_bytes) ? 0 : S;
+}
+
+enum class GemmPath { Small, Ph8, DwSplitK, BatchedDw, FewSplit };
+struct GemmPlan {
+  GemmPath path;
+  int variant;      // (a_kc ? 0 : 2) + (b_kc ? 0 : 1): the operand-layout template arguments
+  int S, Kc, rem;   // split paths: S slabs of Kc K-tiles; the rem leftover K-tiles go one each to slabs 0..rem-1
+  int64_t k8;       // weight-gradient paths: the K the 8-phase launch covers; the rest is the ragged tail
+  int64_t cs_rows;  // Small / Ph8 with colsum: partial rows of the ordered workspace (0: fp32 atomics)
+  EpiSpec spec;     // 8-phase launches: the matched STE_EPI_SPECS entry, or EF_GENERIC
+};
+
+// a.batch >= 1.  The three split / batched plans exclude each other (operand layouts, batch).
+GemmPlan plan_gemm(const ste_gemm_args& a) {
+  GemmPlan pl = {};
+  pl.path = GemmPath::Small;
+  pl.variant = (a.a_kc ? 0 : 2) + (a.b_kc ? 0 : 1);
+  pl.spec = {EF_GENERIC, 0};
+  const int nk = a.K / 64;
+  const int min_tiles = min_tiles_bf16();
+  if (!small_only()) {
+    if ((pl.S = dw_split_slabs(a)) > 0) pl.path = GemmPath::DwSplitK;
+    else if (batched_dw_ok(a)) pl.path = GemmPath::BatchedDw;
+    else if ((pl.S = few_split_slabs(a)) > 0) pl.path = GemmPath::FewSplit;
+    else if (ph8_shape_ok(a) && (long)tiles_256(a) * a.batch >= min_tiles) pl.path = GemmPath::Ph8;
+  }
+  switch (pl.path) {
+    case GemmPath::DwSplitK:
+    case GemmPath::FewSplit:   // the slabs are plain fp32 images: no epilogue flags
+      pl.Kc = nk / pl.S;
+      pl.rem = nk - pl.S * pl.Kc;
+      pl.k8 = (int64_t)nk * 64;
+      pl.spec = match_epi_spec(a.a_kc, a.b_kc, 0, STE_ACT_NONE);
+      break;
+    case GemmPath::BatchedDw:
+      pl.k8 = (int64_t)nk * 64;
+      pl.spec = match_epi_spec(false, false, epi_flags(a), a.act);
+      break;
+    case GemmPath::Ph8:
+      pl.spec = match_epi_spec(true, a.b_kc, epi_flags(a), a.act);
+      [[fallthrough]];
+    case GemmPath::Small:
+      // column sums (bias gradients): with a large enough workspace every tile row writes its two
+      // waves' partial rows there and one ordered pass adds them up (run-to-run deterministic);
+      // without one, fp32 atomics.  The plans above never take a colsum launch, so ws is free
+      // for the partials.
+      if (a.colsum) {
+        const int bm = pl.path == GemmPath::Ph8 ? 256 : small::BM;
+        const int64_t rows = 2 * (int64_t)((a.M + bm - 1) / bm);
+        if (a.ws && a.ws_bytes >= rows * a.batch * a.N * 4) pl.cs_rows = rows;
+      }
+      break;
+  }
+  return pl;
+}
+
+// The 8-phase launch of a split plan: slab s = batch entry s accumulates its Kc (+1) K-tiles
+// into a plain fp32 [M,N] image of ws; ws_bytes = -(rem + 1) marks the launch (operand_bases).
+ste_gemm_args slab_args(const ste_gemm_args& a, const GemmPlan& pl) {
+  ste_gemm_args g = a;
+  g.K = pl.Kc * 64;
+  g.batch = pl.S;
+  g.ws = nullptr;
+  g.ws_bytes = -(int64_t)(pl.rem + 1);
+  g.bias = nullptr; g.C2 = nullptr; g.C3 = nullptr; g.R = nullptr; g.Z = nullptr; g.colsum = nullptr;
+  g.row_scale = nullptr; g.act = 0; g.drop_p = 0.f;
+  g.C = a.ws; g.ldc = a.N; g.strideC = (int64_t)a.M * a.N; g.c_bf16 = 0;
+  g.alpha = 1.f; g.beta = 0.f;
+  return g;
+}
+
+// the ragged K % 64 tail of a weight gradient (k-major operands): += on the small kernel
+int launch_k_tail(const ste_gemm_args& a, int64_t kdone, hipStream_t s) {
+  ste_gemm_args r = a;
+  r.K = (int)(a.K - kdone);
+  r.A = (const bf16*)a.A + kdone * a.lda;
+  r.B = (const bf16*)a.B + kdone * a.ldb;
+  r.beta = 1.f;
+  r.ws = nullptr;
+  return launch_small<false, false>(r, s);
+}
+
+// The argument checks ste_gemm and ste_gemm_mx8 share: positive sizes, and the epilogue contract
+// of 16-B aligned rows for every output / epilogue operand (8 columns per lane; N < 8: every
+// column goes through the element-wise tail path, any alignment works).
+int check_gemm_args(const ste_gemm_args& a) {
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0) return STE_ERR_ARG;
+  auto misaligned = [&a](const void* ptr, int64_t ld, int esz) {
+    return a.N >= 8 && ptr && ((((uintptr_t)ptr) & 15) || ((ld * esz) & 15));
+  };
+  if (misaligned(a.C, a.ldc, a.c_bf16 ? 2 : 4) || misaligned(a.C2, a.ldc2, 2) || misaligned(a.C3, a.ldc3, 2) ||
+      misaligned(a.R, a.ldr, a.r_bf16 ? 2 : 4) || misaligned(a.Z, a.ldz, 2) || misaligned(a.bias, 0, 4))
+    return STE_ERR_SHAPE;
+  return 0;
 }
 
 }  // namespace
-
-static int env_flag(const char* name) {
-  const char* e = STE_AB_ENV(name);
-  return (e && e[0] == '1') ? 1 : 0;
-}
-// STE_GEMM_SMALL_ONLY=1: every shape on the 128x128 kernel; STE_GEMM_2PH=1: the 2-buffer
-// gemm_big schedule instead of the 8-phase one (A/B comparisons in one process).
-static int gemm_mode() {
-  static int mode = -1;
-  if (mode < 0) mode = env_flag("STE_GEMM_SMALL_ONLY") ? 0 : (env_flag("STE_GEMM_2PH") ? 1 : 2);
-  return mode;
-}
 
 extern "C" int ste_gemm_kernel(const ste_gemm_args* args) {
   if (!args) return STE_ERR_ARG;
   ste_gemm_args a = *args;
   if (a.batch <= 0) a.batch = 1;
-  const int variant = (a.a_kc ? 0 : 2) + (a.b_kc ? 0 : 1);
-  if (gemm_mode() == 2 && splitk_plan(a).S > 0) return STE_GEMM_KERNEL_SPLITK + variant;
-  if (gemm_mode() == 2 && few_split(a) && big_ok_shape(a)) return STE_GEMM_KERNEL_SPLITK + variant;
-  if (gemm_mode() == 2 && batched_dw_ok(a)) return STE_GEMM_KERNEL_8PH + variant;
-  if (gemm_mode() > 0 && big_ok(a)) return (gemm_mode() == 2 ? STE_GEMM_KERNEL_8PH : STE_GEMM_KERNEL_BIG) + variant;
-  return STE_GEMM_KERNEL_SMALL + variant;
+  const GemmPlan pl = plan_gemm(a);
+  switch (pl.path) {
+    case GemmPath::Small: return STE_GEMM_KERNEL_SMALL + pl.variant;
+    case GemmPath::Ph8:
+    case GemmPath::BatchedDw: return STE_GEMM_KERNEL_8PH + pl.variant;
+    case GemmPath::DwSplitK:
+    case GemmPath::FewSplit: return STE_GEMM_KERNEL_SPLITK + pl.variant;
+  }
+  return STE_ERR_ARG;
 }
 
 // rocprofv3's (demangled, namespace-stripped) name of the kernel ste_gemm would launch
 extern "C" int ste_gemm_kernel_name(const ste_gemm_args* args, char* buf, int len) {
   if (!args || !buf || len <= 0) return STE_ERR_ARG;
-  const int k = ste_gemm_kernel(args);
-  const int v = k & 3;
-  const char* ak = (v & 2) ? "false" : "true";
-  const char* bk = (v & 1) ? "false" : "true";
-  if (k >= STE_GEMM_KERNEL_8PH) {
-    ste_gemm_args a = *args;
-    int ef = -1, act = 0;
-    if (k >= STE_GEMM_KERNEL_SPLITK) {
-      ef = 0;
-    } else {
-      const int f = epi_flags(a);
-#define STE_MATCH(AK, BK, E, ACT) \
-  if (AK == (bool)a.a_kc && BK == (bool)a.b_kc && f == (E) && a.act == (ACT)) { ef = (E); act = (ACT); }
-      STE_EPI_SPECS(STE_MATCH)
-#undef STE_MATCH
-    }
-    snprintf(buf, len, "gemm_8ph_kernel<%s, %s, %d, %d>", ak, bk, ef, act);
-  } else {
-    snprintf(buf, len, "%s<%s, %s>", k >= STE_GEMM_KERNEL_BIG ? "gemm_big_kernel" : "gemm_bf16_kernel", ak, bk);
-  }
+  ste_gemm_args a = *args;
+  if (a.batch <= 0) a.batch = 1;
+  const GemmPlan pl = plan_gemm(a);
+  const char* ak = (pl.variant & 2) ? "false" : "true";
+  const char* bk = (pl.variant & 1) ? "false" : "true";
+  if (pl.path == GemmPath::Small) snprintf(buf, len, "gemm_bf16_kernel<%s, %s>", ak, bk);
+  else snprintf(buf, len, "gemm_8ph_kernel<%s, %s, %d, %d>", ak, bk, pl.spec.ef, pl.spec.act);
   return 0;
 }
 
@@ -1761,37 +1725,16 @@ extern "C" int ste_gemm(const ste_gemm_args* args, void* stream) {
   if (!args) return STE_ERR_ARG;
   ste_gemm_args a = *args;
   if (a.batch <= 0) a.batch = 1;
-  if (a.M <= 0 || a.N <= 0 || a.K <= 0) return STE_ERR_ARG;
+  if (int e = check_gemm_args(a)) return e;
   // alignment contract (16-B operand chunks)
   if (a.a_kc ? (a.K & 7) || (a.lda & 7) : (a.M & 7) || (a.lda & 7)) return STE_ERR_SHAPE;
   if (a.b_kc ? (a.K & 7) || (a.ldb & 7) : (a.N & 7) || (a.ldb & 7)) return STE_ERR_SHAPE;
   if (a.drop_ld == 0) a.drop_ld = a.N;
-  // epilogue contract: 16-B aligned rows for every output / epilogue operand (8 columns per lane)
-  // (N < 8: every column goes through the element-wise tail path, any alignment works)
-  auto misaligned = [&a](const void* ptr, int64_t ld, int esz) {
-    return a.N >= 8 && ptr && ((((uintptr_t)ptr) & 15) || ((ld * esz) & 15));
-  };
-  if (misaligned(a.C, a.ldc, a.c_bf16 ? 2 : 4) || misaligned(a.C2, a.ldc2, 2) || misaligned(a.C3, a.ldc3, 2) ||
-      misaligned(a.R, a.ldr, a.r_bf16 ? 2 : 4) || misaligned(a.Z, a.ldz, 2) || misaligned(a.bias, 0, 4))
-    return STE_ERR_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  const int mode = gemm_mode();
-  if (mode == 2) {
-    const SplitPlan pl = splitk_plan(a);
-    if (pl.S > 0) {
-      ste_gemm_args g = a;
-      const int64_t kc = (int64_t)pl.Kc * 64;
-      const int nk_all = a.K / 64;
-      const int rem = nk_all - pl.S * pl.Kc;   // whole K-tiles past S·Kc: one each to slabs 0..rem-1
-      g.K = (int)kc;
-      g.batch = pl.S;
-      g.strideA = kc * a.lda;
-      g.strideB = kc * a.ldb;
-      g.ws = nullptr;
-      g.ws_bytes = -(int64_t)(rem + 1);
-      g.C = a.ws; g.ldc = a.N; g.strideC = (int64_t)a.M * a.N; g.c_bf16 = 0;
-      g.alpha = 1.f; g.beta = 0.f;
-      if (int e = launch_8ph<false, false>(g, s)) return e;
+  const GemmPlan pl = plan_gemm(a);
+  switch (pl.path) {
+    case GemmPath::DwSplitK: {
+      if (int e = launch_8ph<false, false>(slab_args(a, pl), pl.spec, s)) return e;
       const int64_t work = (int64_t)a.M * (a.N / 4);
       const dim3 rgrid((unsigned)((work + 255) / 256));
       if (pl.S <= 4)
@@ -1804,78 +1747,39 @@ extern "C" int ste_gemm(const ste_gemm_args* args, void* stream) {
         hipLaunchKernelGGL(splitk_reduce_kernel<16>, rgrid, dim3(256), 0, s, (float*)a.C, a.ldc, a.ws, a.M, a.N, pl.S,
                            a.alpha, a.beta);
       STE_CHECK_LAUNCH();
-      const int64_t kdone = (int64_t)nk_all * 64;
-      if (kdone < a.K) {  // the ragged K % 64 tail: accumulate on the small kernel
-        ste_gemm_args r = a;
-        r.K = (int)(a.K - kdone);
-        r.A = (const bf16*)a.A + kdone * a.lda;
-        r.B = (const bf16*)a.B + kdone * a.ldb;
-        r.beta = 1.f;
-        r.ws = nullptr;
-        return launch_small<false, false>(r, s);
-      }
+      return pl.k8 < a.K ? launch_k_tail(a, pl.k8, s) : 0;
+    }
+    case GemmPath::BatchedDw: {
+      ste_gemm_args g = a;
+      g.K = (int)pl.k8;
+      if (int e = launch_8ph<false, false>(g, pl.spec, s)) return e;
+      return pl.k8 < a.K ? launch_k_tail(a, pl.k8, s) : 0;   // per batch entry
+    }
+    case GemmPath::FewSplit: {
+      if (int e = launch_8ph<true, true>(slab_args(a, pl), pl.spec, s)) return e;
+      const int64_t work = (int64_t)a.M * (a.N / 8);
+      const int blocks = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
+      hipLaunchKernelGGL(splitk_epi_kernel, dim3(blocks), dim3(256), 0, s, a, (const float*)a.ws, pl.S);
+      STE_CHECK_LAUNCH();
       return 0;
     }
+    case GemmPath::Ph8:
+    case GemmPath::Small:
+      break;
   }
-  if (mode == 2 && batched_dw_ok(a)) {
-    ste_gemm_args g = a;
-    const int64_t kdone = (int64_t)(a.K / 64) * 64;
-    g.K = (int)kdone;
-    if (int e = launch_8ph<false, false>(g, s)) return e;
-    if (kdone < a.K) {  // ragged tail: += on the small kernel, per batch entry
-      ste_gemm_args r = a;
-      r.K = (int)(a.K - kdone);
-      r.A = (const bf16*)a.A + kdone * a.lda;
-      r.B = (const bf16*)a.B + kdone * a.ldb;
-      r.beta = 1.f;
-      return launch_small<false, false>(r, s);
-    }
-    return 0;
-  }
-  if (mode == 2 && few_split(a) && big_ok_shape(a)) {
-    const int S = few_split(a);
-    ste_gemm_args g = a;
-    const int nk_all = a.K / 64;
-    g.K = (nk_all / S) * 64;
-    g.batch = S;
-    g.ws = nullptr;
-    g.ws_bytes = -(int64_t)(nk_all - S * (nk_all / S) + 1);
-    g.bias = nullptr; g.C2 = nullptr; g.C3 = nullptr; g.R = nullptr; g.Z = nullptr; g.colsum = nullptr;
-    g.row_scale = nullptr; g.act = 0; g.drop_p = 0.f;
-    g.C = a.ws; g.ldc = a.N; g.strideC = (int64_t)a.M * a.N; g.c_bf16 = 0;
-    g.alpha = 1.f; g.beta = 0.f;
-    if (int e = launch_8ph<true, true>(g, s)) return e;
-    const int64_t work = (int64_t)a.M * (a.N / 8);
-    const int blocks = (int)((work + 255) / 256 < 4096 ? (work + 255) / 256 : 4096);
-    hipLaunchKernelGGL(splitk_epi_kernel, dim3(blocks), dim3(256), 0, s, a, (const float*)a.ws, S);
-    STE_CHECK_LAUNCH();
-    return 0;
-  }
-  // column sums (bias gradients): with a large enough workspace every tile row writes its two waves'
-  // partial rows there and one ordered pass adds them up (run-to-run deterministic); without one,
-  // fp32 atomics.  The plans above never take a colsum launch, so ws is free for the partials.
-  const bool use_big = mode > 0 && big_ok(a);
-  int64_t cs_rows = 0;
-  if (a.colsum) {
-    const int bm = use_big ? 256 : small::BM;
-    const int64_t rows = 2 * (int64_t)((a.M + bm - 1) / bm);
-    if (a.ws && a.ws_bytes >= rows * a.batch * a.N * 4) cs_rows = rows;
-  }
-  if (!cs_rows) a.ws = nullptr;
+  if (!pl.cs_rows) a.ws = nullptr;
   int e;
-  if (use_big) {
-    if (mode == 2) e = a.b_kc ? launch_8ph<true, true>(a, s) : launch_8ph<true, false>(a, s);
-    else e = a.b_kc ? launch_big<true, true>(a, s) : launch_big<true, false>(a, s);
-  } else if (a.a_kc && a.b_kc) {
-    e = launch_small<true, true>(a, s);
-  } else if (a.a_kc && !a.b_kc) {
-    e = launch_small<true, false>(a, s);
-  } else if (!a.a_kc && !a.b_kc) {
-    e = launch_small<false, false>(a, s);
+  if (pl.path == GemmPath::Ph8) {
+    e = pl.variant == 0 ? launch_8ph<true, true>(a, pl.spec, s) : launch_8ph<true, false>(a, pl.spec, s);
   } else {
-    e = launch_small<false, true>(a, s);
+    switch (pl.variant) {
+      case 0: e = launch_small<true, true>(a, s); break;
+      case 1: e = launch_small<true, false>(a, s); break;
+      case 2: e = launch_small<false, true>(a, s); break;
+      default: e = launch_small<false, false>(a, s); break;
+    }
   }
-  if (e == 0 && cs_rows) e = ste_rowsum_ordered(a.ws, cs_rows, a.N, a.batch, a.colsum, stream);
+  if (e == 0 && pl.cs_rows) e = ste_rowsum_ordered(a.ws, pl.cs_rows, a.N, a.batch, a.colsum, stream);
   return e;
 }
 
@@ -1894,9 +1798,11 @@ extern "C" int64_t ste_gemm_colsum_ws_floats(const ste_gemm_args* args) {
 // ============================================================ MX-fp8 GEMM (config 5)
 // Y = X·Wᵀ with both operands OCP e4m3 (KC, k contiguous) and E8M0 block scales, one per 32
 // consecutive k of a row ([rows][K/32] bytes): v_mfma_scale_f32_16x16x128_f8f6f4, which runs at
-// twice the bf16 MFMA rate (MI355X_MICROARCH.md, matrix cores).  Same 256x256 tile, 8 waves
-// (2(M) x 4(N), 128x64 each), 2-deep global_load_lds ring and general epilogue as gemm_big;
-// a K-tile is 128 fp8 = 128 B per row, so the LDS image and its swizzle are gemm_big's.
+// twice the bf16 MFMA rate (MI355X_MICROARCH.md, matrix cores).  The single-stage kernel:
+// 256x256 tile, 8 waves (2(M) x 4(N), 128x64 each), a 2-deep global_load_lds ring drained with
+// vmcnt(0) every K-tile, and the general run-time epilogue, 32 rows per wave per pass.  A K-tile
+// is 128 fp8 = 128 B per row, so the LDS image is the bf16 KC one: [256 rows][128 B], lane-linear
+// 1 KiB pieces of 8 rows, the 16-B chunk of row r stored at chunk ^ (r & 7).
 // Operand lane map of the 16x16x128 form (probed on the box with exact integer data,
 // scratch/mx8_probe.hip): lane l holds row l&15, bytes 0-15 = k 16g..16g+15 and bytes 16-31 =
 // k 64+16g..+15 (g = l>>4); the scale of row r's k-block kb is read from lane r + 16·kb.  So
@@ -1907,6 +1813,7 @@ constexpr int TILE_BYTES = BM * BK;             // 32 KiB per operand per stage
 constexpr int SC_BYTES = BM * 4;                // 4 scale bytes per row per K-tile
 constexpr int STAGE_BYTES = 2 * TILE_BYTES + 2 * SC_BYTES;
 constexpr int LDS_BYTES = 2 * STAGE_BYTES;      // 132 KiB
+constexpr int EPI_ROWS = 32;                    // rows staged per epilogue pass per wave
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x4v __attribute__((ext_vector_type(4)));
 
@@ -2002,9 +1909,10 @@ __global__ __launch_bounds__(mx8::NT, 1) void gemm_mx8_kernel(ste_gemm_args p, c
     __syncthreads();
   }
 
-  float* epi = reinterpret_cast<float*>(smem) + wave * big::EPI_ROWS * EPI_LD;
+  // epilogue: 4 passes of 32 rows x 64 cols per wave through LDS
+  float* epi = reinterpret_cast<float*>(smem) + wave * EPI_ROWS * EPI_LD;
   Csum csum = {};
-  constexpr bool EPI_SKIP = false;
+  // (explicit passes: a rolled pass loop would index acc dynamically and demote it to scratch)
 #define EPI_COL0 (n0 + wn * 64)
 #define EPI_COL1 (n0 + wn * 64 + 32)
 #define STE_EPI_PASS(PS)                                                                                     \
@@ -2018,9 +1926,9 @@ __global__ __launch_bounds__(mx8::NT, 1) void gemm_mx8_kernel(ste_gemm_args p, c
     }                                                                                                        \
     __builtin_amdgcn_s_waitcnt(0xc07f);                                                                      \
     __builtin_amdgcn_wave_barrier();                                                                         \
-    for (int hh = 0; hh < big::EPI_ROWS; hh += 16) {                                                         \
-      if (!EPI_SKIP) epilogue_tile(p, epi + hh * EPI_LD, 16, m0 + wm * 128 + (PS) * big::EPI_ROWS + hh,     \
-                                   EPI_COL0, EPI_COL1, batch, lane, csum, EPI_LD, false, q8o.q ? &q8o : nullptr);                                   \
+    for (int hh = 0; hh < EPI_ROWS; hh += 16) {                                                              \
+      epilogue_tile(p, epi + hh * EPI_LD, 16, m0 + wm * 128 + (PS) * EPI_ROWS + hh, EPI_COL0, EPI_COL1,      \
+                    batch, lane, csum, EPI_LD, false, q8o.q ? &q8o : nullptr);                               \
     }                                                                                                        \
     __builtin_amdgcn_s_waitcnt(0xc07f);                                                                      \
     __builtin_amdgcn_wave_barrier();                                                                         \
@@ -2056,19 +1964,14 @@ extern "C" int ste_mx8_quant(const void* x, int64_t ldx, int rows, int K, void* 
 }
 
 namespace {
-// STE_MX8_8PH=0: the single-stage gemm_mx8_kernel for every shape (A/B runs)
 // Round 5: until the scale-select fix (mfma_mx) the persistent 8-phase MX kernel returned wrong
 // products at every shape it was planned for (>= 240 tiles), in every tree since round 3
 // (profiles/r5q_mx8_bisect.txt); tests/test_kernels_gpu.py::test_gemm_mx8_8ph_specs now checks
 // each of its compile-time epilogues there.  libste_ab.so with STE_MX8_8PH=0: the single-stage
 // gemm_mx8_kernel for every MX GEMM (A/B)
 bool mx8_8ph_on() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = STE_AB_ENV("STE_MX8_8PH");
-    v = (e && e[0] == '0') ? 0 : 1;
-  }
-  return v == 1;
+  static const bool off = env_is(STE_AB_ENV("STE_MX8_8PH"), '0');
+  return !off;
 }
 // MX-fp8 on the persistent 8-phase kernel: the e4m3 operands passed as bf16 pairs (K, lda, ldb
 // halved), compile-time epilogues for the Conformer forward GEMMs (and, for the opt-in MX-fp8
@@ -2082,36 +1985,41 @@ bool mx8_8ph_on() {
   X(EF_BIAS | EF_C2 | EF_CBF16 | EF_Q8 | EF_NOC, STE_ACT_SWISH)  /* FFN in, frozen: fp8 copy only */ \
   X(EF_Z | EF_CBF16, STE_ACT_SWISH_BWD)                          /* dz (fp8_bwd A/B) */
 
-int mx8_ef(const ste_gemm_args& a, bool q_out) { return epi_flags(a) | (q_out ? EF_Q8 : 0) | (a.C ? 0 : EF_NOC); }
-
-// Host-side plan: the persistent 8-phase MX kernel, or the single-stage gemm_mx8_kernel.  The
-// 8-phase kernel's operand and scale DMA sources are 32-bit byte offsets from the operand base
-// (stage_half<.., O32>, stage_scales), so each operand (fp8 bytes, M·lda / N·ldb) must stay
-// below 4 GiB; larger operands, other epilogues and shapes under 240 tiles take the single-stage
-// kernel (64-bit addressing)
-bool mx8_8ph_plan(const ste_gemm_args& a, bool q_out) {
-  if (!mx8_8ph_on() || gemm_mode() != 2) return false;
-  const int64_t nb = (int64_t)((a.M + 255) / 256) * ((a.N + 255) / 256);
-  if (nb < g_min_tiles_mx8 || (q_out && (a.N % 256) != 0)) return false;   // fp8 copy per FULL 256-column tile
-  const uint64_t lim = 1ull << 32;
-  if ((uint64_t)a.M * (uint64_t)a.lda >= lim || (uint64_t)a.N * (uint64_t)a.ldb >= lim) return false;
-  const int ef = mx8_ef(a, q_out);
-#define STE_MX_MATCH(E, ACT) if (ef == (E) && a.act == (ACT)) return true;
+// The one match against STE_MX8_SPECS, shared by the plan and (through the plan's result) the
+// launch; EF_GENERIC: no compile-time MX epilogue.
+EpiSpec match_mx8_spec(const ste_gemm_args& a, bool q_out) {
+  const int ef = epi_flags(a) | (q_out ? EF_Q8 : 0) | (a.C ? 0 : EF_NOC);
+#define STE_MX_MATCH(E, ACT) if (ef == (E) && a.act == (ACT)) return {(E), (ACT)};
   STE_MX8_SPECS(STE_MX_MATCH)
 #undef STE_MX_MATCH
-  return false;
+  return {EF_GENERIC, 0};
 }
 
-int launch_mx8_8ph(const ste_gemm_args& a8, const Mx8Args& mx, hipStream_t s) {
+// Host-side plan: the persistent 8-phase MX kernel (true, its epilogue in spec), or the
+// single-stage gemm_mx8_kernel.  The 8-phase kernel's operand and scale DMA sources are 32-bit
+// byte offsets from the operand base (stage_half<.., O32>, stage_scales), so each operand (fp8
+// bytes, M·lda / N·ldb) must stay below 4 GiB; larger operands, other epilogues and shapes under
+// 240 tiles take the single-stage kernel (64-bit addressing)
+bool mx8_8ph_plan(const ste_gemm_args& a, bool q_out, EpiSpec& spec) {
+  spec = {EF_GENERIC, 0};
+  if (!mx8_8ph_on() || small_only()) return false;
+  if (tiles_256(a) < g_min_tiles_mx8.load() || (q_out && (a.N % 256) != 0)) return false;   // fp8 copy per FULL 256-column tile
+  const uint64_t lim = 1ull << 32;
+  if ((uint64_t)a.M * (uint64_t)a.lda >= lim || (uint64_t)a.N * (uint64_t)a.ldb >= lim) return false;
+  spec = match_mx8_spec(a, q_out);
+  return spec.ef != EF_GENERIC;
+}
+
+// spec: the plan's; a spec without an instantiation cannot come from mx8_8ph_plan and is an error
+int launch_mx8_8ph(const ste_gemm_args& a8, const Mx8Args& mx, EpiSpec spec, hipStream_t s) {
   ste_gemm_args a = a8;
   a.K = a8.K / 2;
   a.lda = a8.lda / 2;
   a.ldb = a8.ldb / 2;
-  const int nb = ((a.M + 255) / 256) * ((a.N + 255) / 256);
+  const int nb = tiles_256(a);
   const int grid = nb < num_cus() ? nb : num_cus();
-  const int ef = mx8_ef(a, mx.q8.q != nullptr);
 #define STE_MX(E, ACT)                                                                                          \
-  if (ef == (E) && a.act == (ACT)) {                                                                            \
+  if (spec.ef == (E) && spec.act == (ACT)) {                                                                    \
     hipLaunchKernelGGL((gemm_8ph_kernel<true, true, (E), (ACT), true>), dim3(grid), dim3(ph8::NT), ph8::LDS_BYTES, \
                        s, a, mx);                                                                               \
     STE_CHECK_LAUNCH();                                                                                         \
@@ -2119,21 +2027,22 @@ int launch_mx8_8ph(const ste_gemm_args& a8, const Mx8Args& mx, hipStream_t s) {
   }
   STE_MX8_SPECS(STE_MX)
 #undef STE_MX
-  return -1;   // other epilogues: the single-stage kernel
+  return STE_ERR_ARG;
 }
 }  // namespace
 
 extern "C" int ste_gemm_plan_min_tiles(int bf16_tiles, int mx8_tiles, int* prev_bf16, int* prev_mx8) {
   if (prev_bf16) *prev_bf16 = min_tiles_bf16();
-  if (prev_mx8) *prev_mx8 = g_min_tiles_mx8;
-  if (bf16_tiles > 0) g_min_tiles_bf16 = bf16_tiles;
-  if (mx8_tiles > 0) g_min_tiles_mx8 = mx8_tiles;
+  if (prev_mx8) *prev_mx8 = g_min_tiles_mx8.load();
+  if (bf16_tiles > 0) g_min_tiles_bf16.store(bf16_tiles);
+  if (mx8_tiles > 0) g_min_tiles_mx8.store(mx8_tiles);
   return 0;
 }
 
 extern "C" int ste_gemm_mx8_kernel(const ste_gemm_args* args, int q_out) {
   if (!args) return STE_ERR_ARG;
-  return mx8_8ph_plan(*args, q_out != 0) ? 1 : 0;
+  EpiSpec spec;
+  return mx8_8ph_plan(*args, q_out != 0, spec) ? 1 : 0;
 }
 
 extern "C" int ste_gemm_mx8(const ste_gemm_args* args, const void* a_scales, const void* b_scales, void* q_out,
@@ -2142,25 +2051,20 @@ extern "C" int ste_gemm_mx8(const ste_gemm_args* args, const void* a_scales, con
   if (q_out && ((args->N & 127) || (((uintptr_t)q_out) & 7) || args->colsum)) return STE_ERR_SHAPE;
   ste_gemm_args a = *args;
   a.batch = 1;
-  if (a.M <= 0 || a.N <= 0 || a.K <= 0) return STE_ERR_ARG;
+  if (int e = check_gemm_args(a)) return e;
   if (!a.a_kc || !a.b_kc || (a.K & 127) || (a.lda & 15) || (a.ldb & 15) || a.lda < a.K || a.ldb < a.K || a.ws)
     return STE_ERR_SHAPE;
-  if (a.drop_ld == 0) a.drop_ld = a.N;
-  auto misaligned = [&a](const void* ptr, int64_t ld, int esz) {
-    return a.N >= 8 && ptr && ((((uintptr_t)ptr) & 15) || ((ld * esz) & 15));
-  };
-  if (misaligned(a.C, a.ldc, a.c_bf16 ? 2 : 4) || misaligned(a.C2, a.ldc2, 2) || misaligned(a.C3, a.ldc3, 2) ||
-      misaligned(a.R, a.ldr, a.r_bf16 ? 2 : 4) || misaligned(a.Z, a.ldz, 2) || misaligned(a.bias, 0, 4) ||
-      (((uintptr_t)a.A) & 15) || (((uintptr_t)a.B) & 15) || (((uintptr_t)a_scales) & 3) ||
+  if ((((uintptr_t)a.A) & 15) || (((uintptr_t)a.B) & 15) || (((uintptr_t)a_scales) & 3) ||
       (((uintptr_t)b_scales) & 3))
     return STE_ERR_SHAPE;
-  const int nb = ((a.M + 255) / 256) * ((a.N + 255) / 256);
+  if (a.drop_ld == 0) a.drop_ld = a.N;
   const Q8Out q8o = {(uint8_t*)q_out, (uint8_t*)q_scales, a.N};
-  if (mx8_8ph_plan(a, q_out != nullptr)) {
+  EpiSpec spec;
+  if (mx8_8ph_plan(a, q_out != nullptr, spec)) {
     const Mx8Args mx = {(const uint8_t*)a_scales, (const uint8_t*)b_scales, a.K / 32, a.K / 32, q8o};
-    if (launch_mx8_8ph(a, mx, (hipStream_t)stream) == 0) return 0;
+    return launch_mx8_8ph(a, mx, spec, (hipStream_t)stream);
   }
-  hipLaunchKernelGGL(gemm_mx8_kernel, dim3(nb), dim3(mx8::NT), mx8::LDS_BYTES, (hipStream_t)stream, a,
+  hipLaunchKernelGGL(gemm_mx8_kernel, dim3(tiles_256(a)), dim3(mx8::NT), mx8::LDS_BYTES, (hipStream_t)stream, a,
                      (const uint8_t*)a_scales, (const uint8_t*)b_scales, q8o);
   STE_CHECK_LAUNCH();
   return 0;

@@ -124,6 +124,45 @@ def test_gemm_split_policies(lib):
     assert k(C.byref(b)) == 3
 
 
+_FFN = dict(M=31936, N=4096, K=1024, batch=1, a_kc=1, b_kc=1)            # 125 x 16 tiles
+_FEW = dict(M=8192, N=768, K=6144, batch=1, a_kc=1, b_kc=1, ws=1, ws_bytes=80 << 20)
+_DW = dict(M=4096, N=1024, K=31936, batch=1, a_kc=0, b_kc=0, ws=1, ws_bytes=80 << 20)
+_BDW = dict(M=512, N=1536, K=15999, batch=64, a_kc=0, b_kc=0)
+_DZ = dict(_FFN, Z=1, colsum=1, c_bf16=1, act=12, ws=1, ws_bytes=80 << 20)   # act 12: STE_ACT_GELU_BWD
+# (case, GemmArgs fields, ste_gemm_kernel id, ste_gemm_kernel_name): every plan path at its boundary
+GEMM_PLAN_TABLE = [
+    ("8ph_spec", _FFN, 8, b"gemm_8ph_kernel<true, true, 0, 0>"),
+    ("8ph_spec_bkm", dict(_FFN, b_kc=0), 9, b"gemm_8ph_kernel<true, false, 0, 0>"),
+    ("8ph_generic", dict(_FFN, bias=1, row_scale=1), 8, b"gemm_8ph_kernel<true, true, -1, 0>"),
+    ("8ph_generic_bkm", dict(_FFN, bias=1, row_scale=1, b_kc=0), 9, b"gemm_8ph_kernel<true, false, -1, 0>"),
+    ("8ph_colsum_ws", _DZ, 8, b"gemm_8ph_kernel<true, true, 548, 12>"),
+    ("8ph_colsum_ws_bkm", dict(_DZ, b_kc=0), 9, b"gemm_8ph_kernel<true, false, -1, 0>"),
+    ("few", _FEW, 12, b"gemm_8ph_kernel<true, true, 0, 0>"),
+    ("few_39_ktiles", dict(_FEW, K=39 * 64), 0, b"gemm_bf16_kernel<true, true>"),
+    ("few_m2047", dict(_FEW, M=2047), 0, b"gemm_bf16_kernel<true, true>"),
+    ("dw_split", _DW, 15, b"gemm_8ph_kernel<false, false, 0, 0>"),
+    ("dw_split_k960", dict(_DW, K=960), 3, b"gemm_bf16_kernel<false, false>"),
+    ("dw_split_bias", dict(_DW, bias=1), 3, b"gemm_bf16_kernel<false, false>"),
+    ("batched_dw", _BDW, 11, b"gemm_8ph_kernel<false, false, 0, 0>"),
+    ("batched_dw_b4", dict(_BDW, batch=4), 3, b"gemm_bf16_kernel<false, false>"),
+    ("small_ragged_k", dict(_FFN, K=1000), 0, b"gemm_bf16_kernel<true, true>"),
+    ("small_batched_kc", dict(_FEW, batch=2), 0, b"gemm_bf16_kernel<true, true>"),
+]
+
+
+@pytest.mark.parametrize("fields,kid,name", [c[1:] for c in GEMM_PLAN_TABLE], ids=[c[0] for c in GEMM_PLAN_TABLE])
+def test_gemm_plan_table(lib, fields, kid, name):
+    """ste_gemm_kernel and ste_gemm_kernel_name (host-only, no launch) over every plan path at its
+    boundary.  The expected ids and names are those the library returned before the host-side
+    plan was gathered into one function; without a GPU the plan assumes 256 CUs, the MI355X's."""
+    a = lib.GemmArgs()
+    for f, v in fields.items():
+        setattr(a, f, v)
+    buf = C.create_string_buffer(128)
+    assert lib.fn("ste_gemm_kernel_name")(C.byref(a), buf, 128) == 0
+    assert (lib.fn("ste_gemm_kernel")(C.byref(a)), buf.value) == (kid, name)
+
+
 def test_gemm_mx8_plan(lib):
     """ste_gemm_mx8's kernel choice (no launch): the 8-phase MX kernel addresses its operands by
     32-bit byte offsets, so an operand of 4 GiB or more must take the single-stage kernel
@@ -155,7 +194,8 @@ def test_gemm_plan_min_tiles(lib):
     f = lib.fn("ste_gemm_plan_min_tiles")
     pb, pm = C.c_int(), C.c_int()
     assert f(0, 0, C.byref(pb), C.byref(pm)) == 0
-    assert (pb.value, pm.value) == (240, 240)
+    # the A/B build (only) takes its bf16 default from STE_GEMM_MIN_TILES
+    assert (pb.value, pm.value) == (int(lib.ab_env("STE_GEMM_MIN_TILES", "240")), 240)
     k, km = lib.fn("ste_gemm_kernel"), lib.fn("ste_gemm_mx8_kernel")
     a = lib.GemmArgs()   # FFN-in of a B = 2 c2 instance: 998 rows, 4 x 16 tiles, bias + swish + C2, bf16 out
     a.M, a.N, a.K, a.batch, a.a_kc, a.b_kc, a.lda, a.ldb = 998, 4096, 1024, 1, 1, 1, 1024, 1024
