@@ -582,6 +582,9 @@ int ste_w2v_wnorm_bwd(const float* dwr, const float* v, const float* g, const fl
                       float* dv, float* dg, void* stream);
 /* Frame mask of the conv stack (:997-1036): per clip L = Σ mask[b, :] (N if mask is NULL) pushed
  * through floor((L - k)/s) + 1 per layer; maskf/mask32 [B*Tf] = t < L (either may be NULL).
+ * A clip shorter than the receptive field ends at L <= 0: transformers then sets index L - 1,
+ * which wraps around, so Tf + L frames are valid (L = 0: every frame, L = -1: all but the last);
+ * transformers raises for L < -Tf + 1, where the count here is clamped at 0.
  * kernels/strides are HOST arrays of nconv <= 16 entries. */
 int ste_w2v_frame_mask(const int64_t* mask, int B, int N, int Tf, int nconv, const int* kernels, const int* strides,
                        float* maskf, int32_t* mask32, void* stream);

@@ -409,8 +409,10 @@ struct ConvStack {
   int k[16], s[16];
 };
 
-// per clip: valid samples = Σ mask (or N), conv output lengths, mask[b, t] = t < L
-// (L <= 0: transformers' index -1 assignment marks every frame valid)
+// per clip: valid samples = Σ mask (or N), conv output lengths, mask[b, t] = t < L.
+// L <= 0 (a clip shorter than the receptive field): transformers sets index L - 1, which wraps
+// around to Tf + L - 1, so Tf + L frames are valid (L = 0: all Tf, L = -1: all but the last).
+// Below -Tf transformers raises an IndexError; outside its domain the count is clamped at 0.
 __global__ __launch_bounds__(NT) void frame_mask_kernel(const int64_t* __restrict__ mask, int N, int Tf, ConvStack cs,
                                                         float* __restrict__ maskf, int* __restrict__ mask32) {
   __shared__ long long sred[NT];
@@ -431,7 +433,7 @@ __global__ __launch_bounds__(NT) void frame_mask_kernel(const int64_t* __restric
     const long long d = L - cs.k[i];
     L = (d >= 0 ? d / cs.s[i] : -((-d + cs.s[i] - 1) / cs.s[i])) + 1;  // floor division
   }
-  if (L <= 0) L = Tf;
+  if (L <= 0) L = L + Tf > 0 ? L + Tf : 0;
   for (int t = threadIdx.x; t < Tf; t += NT) {
     const int on = t < L;
     if (maskf) maskf[(int64_t)b * Tf + t] = (float)on;

@@ -51,6 +51,20 @@ def drop_scale(seed: int, idx: np.ndarray, p: float) -> np.ndarray:
     return keep.astype(np.float32) / (1.0 - p)
 
 
+def w2v2_frame_mask_ref(mask, Tf, kernels, strides):
+    """Frame mask [B, Tf] (bool) of a sample mask [B, N] (int64), transformers' rule restated
+    (Wav2Vec2Model._get_feature_vector_attention_mask, pinned to it by tests/test_w2v2_cpu.py):
+    the valid-sample count through floor((L - k)/s) + 1 per conv layer, then a 1 at index L - 1
+    (a negative index wraps around, as torch index assignment does) and flip-cumsum-flip."""
+    L = mask.sum(-1).to(torch.long)
+    for k, s in zip(kernels, strides):
+        L = torch.div(L - k, s, rounding_mode="floor") + 1
+    B = mask.shape[0]
+    m = torch.zeros(B, Tf, dtype=torch.long)
+    m[torch.arange(B), L.cpu() - 1] = 1
+    return m.flip([-1]).cumsum(-1).flip([-1]).bool()
+
+
 def attention_ref(q, k, v, mask, E=None, left=64, right=8, drop_p=0.0, seed=0):
     """q,k,v [B,T,H,64] fp32; mask [B,T] (1 valid) or None; returns o [B,T,H,64]."""
     B, T, H, D = q.shape

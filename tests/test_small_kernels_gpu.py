@@ -1,7 +1,8 @@
 """Unit parity of the small C-ABI kernels that the model tests otherwise reach only inside a whole
 step: SpecAugment row masking, the in-batch InfoNCE, the epoch pair metrics, the small fp32
-row-matrix product, strided axpby and the fp32 -> bf16 cast — each against a float64 torch
-reference of the contract include/ste.h states for it."""
+row-matrix product, strided axpby, the fp32 -> bf16 cast, the strided 2-D copy, the row scaling
+and the int64 mask conversion — each against a float64 torch reference of the contract
+include/ste.h states for it (pure moves and single fp32 operations: bit-exact)."""
 import pytest
 import torch
 
@@ -113,3 +114,48 @@ def test_cast_bf16_round_to_nearest_even(ops):
     y = torch.empty(x.numel(), device=DEV, dtype=torch.bfloat16)
     ops.cast_bf16(x, y)
     assert torch.equal(y, x.bfloat16())
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_copy2d_values(ops, dtype):
+    """ste_copy2d: 4- and 2-byte elements between views of different row strides, 300 columns (more
+    than the 256 threads of a row's block); bytes outside the window stay."""
+    torch.manual_seed(6)
+    big_y = torch.randn(50, 340, device=DEV).to(dtype)
+    big_x = torch.randn(50, 310, device=DEV).to(dtype)
+    y, x = big_y[:, 10:310], big_x[:, 4:304]       # row strides 340 / 310, 300 columns
+    rest = big_y.clone()
+    ops.copy2d(y, x)
+    assert torch.equal(y, x)
+    assert torch.equal(big_y[:, :10], rest[:, :10]) and torch.equal(big_y[:, 310:], rest[:, 310:])
+
+
+@pytest.mark.parametrize("cols,ld", [(1028, 1032), (7, 12), (8, 10)])
+def test_scale_rows_values(cols, ld):
+    """ste_scale_rows: x[r, c] *= scale[r] for c < cols (one fp32 multiply: bit-exact) on the 16-B
+    vector path (cols and ld multiples of 4; 1028 columns: a second pass of the 256 threads) and
+    the scalar path (cols = 7, or ld = 10); columns past cols stay."""
+    from speech_transcript_embeddings_amd import _lib
+    torch.manual_seed(cols)
+    rows = 37
+    big = torch.randn(rows, ld, device=DEV)
+    sc = torch.randn(rows, device=DEV)
+    want = big.clone()
+    want[:, :cols] *= sc[:, None]
+    assert big.data_ptr() % 16 == 0
+    _lib.call("ste_scale_rows", big.data_ptr(), sc.data_ptr(), rows, cols, ld, _lib.stream_ptr())
+    assert torch.equal(big, want)
+
+
+def test_mask_i64_to_f32_values():
+    """ste_mask_i64_to_f32: f = (m != 0) as float, i32 = (m != 0) as int32, either output alone."""
+    from speech_transcript_embeddings_amd import _lib
+    torch.manual_seed(7)
+    n = 1000
+    m = torch.randint(0, 3, (n,), device=DEV, dtype=torch.int64)
+    for want_f, want_i in ((True, True), (True, False), (False, True)):
+        f = torch.full((n,), 7.0, device=DEV) if want_f else None
+        i32 = torch.full((n,), 7, device=DEV, dtype=torch.int32) if want_i else None
+        _lib.call("ste_mask_i64_to_f32", m.data_ptr(), _lib.ptr(f), _lib.ptr(i32), n, _lib.stream_ptr())
+        assert f is None or torch.equal(f, (m != 0).float())
+        assert i32 is None or torch.equal(i32, (m != 0).int())

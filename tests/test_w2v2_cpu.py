@@ -65,6 +65,25 @@ def test_frame_lengths_match_transformers(n):
     assert W2V2Config().frames(n)[-1] == want
 
 
+def test_frame_mask_reference_matches_transformers():
+    """kref.w2v2_frame_mask_ref (the reference of the ste_w2v_frame_mask kernel test) equals
+    transformers' _get_feature_vector_attention_mask, including the clips shorter than the
+    receptive field: the conv output length L <= 0 indexes from the end, so L = 0 (10..29 valid
+    samples here) marks all 19 frames and L = -1 (0..9 samples) all but the last."""
+    from kref import w2v2_frame_mask_ref
+    ks, ss = (10, 3, 2), (5, 2, 2)
+    with torch.device("meta"):
+        hf = _hf_model(dict(conv_dim=(8, 8, 8), conv_kernel=ks, conv_stride=ss, num_feat_extract_layers=3,
+                            hidden_size=16, num_hidden_layers=1, num_attention_heads=1, intermediate_size=16))
+    N, Tf = 400, 19
+    sums = [0, 1, 9, 10, 14, 25, 26, 399, 400]
+    mask = (torch.arange(N)[None, :] < torch.tensor(sums)[:, None]).long()
+    want = hf._get_feature_vector_attention_mask(Tf, mask)
+    got = w2v2_frame_mask_ref(mask, Tf, ks, ss)
+    assert torch.equal(got, want)
+    assert got.sum(-1).tolist() == [18, 18, 18, 19, 19, 19, 19, 19, 19]
+
+
 def test_unsupported_variants_raise():
     from speech_transcript_embeddings_amd.modules import W2V2Config
     for kw in ({"feat_extract_norm": "layer"}, {"conv_bias": True}, {"do_stable_layer_norm": True}):
