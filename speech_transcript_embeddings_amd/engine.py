@@ -99,11 +99,7 @@ class Engine:
     @property
     def ws(self):
         """Split-K workspace of the CURRENT stream (the text and audio backward run concurrently)."""
-        key = torch.cuda.current_stream(self.s.device).cuda_stream if self.s.device.type == "cuda" else 0
-        w = self._ws.get(key)
-        if w is None:
-            w = self._ws[key] = torch.empty(self.WS_BYTES // 4, device=self.s.device, dtype=F32)
-        return w
+        return ops.stream_ws(self.s.device, self.WS_BYTES // 4, cache=self._ws)
 
     def _await_params(self, *names):
         """Order the current stream after the overlapped optimizer's update of these parameter
@@ -133,7 +129,7 @@ class Engine:
 
     def _dw(self, dy_b, x_b, wname, fused=1):
         """dW[N,K] += dyᵀ·x into the flat gradient buffer (if the weight receives gradients)."""
-        g = self.s.fused(wname, fused, "g") if fused > 1 else self.s.g(wname)
+        g = self.s.fused(wname, fused, "g")
         if g is None:
             return
         g2 = g.view(g.shape[0], -1)
@@ -162,7 +158,7 @@ class Engine:
         return out
 
     def _db(self, x, bname, fused=1):
-        g = self.s.fused(bname, fused, "g") if fused > 1 else self.s.g(bname)
+        g = self.s.fused(bname, fused, "g")
         if g is not None:
             ops.colsum(x, g)
 
@@ -262,7 +258,7 @@ class Engine:
             if fp8:
                 xq = xb if isinstance(xb, tuple) else ops.mx8_quant(xb)
                 return ops.linear_mx8(xq, s.wq(wname, count), bias, **kw)
-            return ops.linear(xb, s.fused(wname, count, "w") if count > 1 else s.w(wname), bias, **kw)
+            return ops.linear(xb, s.fused(wname, count, "w"), bias, **kw)
 
         def ffn_in(a, wname, bname, z):
             """FFN intermediate (swish): bf16 output, and under fp8_gemm the MX-fp8 copy the output
@@ -648,7 +644,7 @@ class Engine:
         """dW += dYᵀ·X of a text Linear from [hi | lo] split images of both operands, to ~fp32:
         dY_hiᵀX_hi + dY_loᵀX_hi + dY_hiᵀX_lo (the lo·lo term is below fp32 rounding), three
         k-major GEMMs accumulating into the flat gradient buffer."""
-        g = self.s.fused(wname, fused, "g") if fused > 1 else self.s.g(wname)
+        g = self.s.fused(wname, fused, "g")
         if g is None:
             return
         g2 = g.view(g.shape[0], -1)

@@ -32,21 +32,24 @@ def _ld(t: torch.Tensor) -> int:
 # A/B runs and tests; STE_ATOMIC_SUMS=1 sets it for a whole run under the A/B build).  Default: ordered partial sums,
 # run-to-run deterministic gradients.
 ATOMIC_SUMS = _lib.ab_env("STE_ATOMIC_SUMS", "0") == "1"
-_RED_WS = {}
+_WS = {}
+
+
+def stream_ws(dev, floats, slot=0, floor=0, cache=_WS):
+    """fp32 workspace of (the current stream, slot), at least `floats` long, grown on demand (never
+    below `floor`).  Launches of one stream run in order, so consecutive users of a slot share the
+    buffer; concurrent streams get their own."""
+    key = (torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0, slot)
+    w = cache.get(key)
+    if w is None or w.numel() < floats:
+        w = cache[key] = torch.empty(max(int(floats), floor), device=dev, dtype=F32)
+    return w
 
 
 def _red_ws(dev, floats):
-    """Partial-sum workspace of the current stream for the ordered reductions (GEMM bias gradients,
-    ste_colsum, depthwise-conv / embedding / SpecAugment gradients), grown on demand.  Launches of
-    one stream run in order, so consecutive reductions reuse it; concurrent streams get their own.
-    None under ATOMIC_SUMS."""
-    if ATOMIC_SUMS or floats <= 0:
-        return None
-    key = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
-    w = _RED_WS.get(key)
-    if w is None or w.numel() < floats:
-        w = _RED_WS[key] = torch.empty(max(int(floats), 1 << 20), device=dev, dtype=F32)
-    return w
+    """Partial-sum workspace for the ordered reductions (GEMM bias gradients, ste_colsum,
+    depthwise-conv / embedding / SpecAugment gradients).  None under ATOMIC_SUMS."""
+    return None if ATOMIC_SUMS or floats <= 0 else stream_ws(dev, floats, "red", floor=1 << 20)
 
 
 def _ws_args(w):
@@ -319,21 +322,11 @@ def layernorm_fwd_pair(first: dict, second: dict):
 LN_ATOMIC_COLSUMS = _lib.ab_env("STE_LN_ATOMIC", "0") == "1"
 
 
-_LN_WS_BUF = {}
-
-
 def _ln_ws(dev, rows, cols, slot):
-    """Column-partial workspace of a LayerNorm backward, one per (stream, slot), grown on demand:
-    the launches of one stream run in order, so consecutive backwards reuse one buffer (a pair
-    kernel's two LayerNorms take slots 0 and 1); concurrent streams get their own.  Its size
-    (ste_layernorm_bwd_ws_floats) stops growing once rows reach the kernel's block count, so
-    batches padded to different lengths share one buffer instead of one each."""
-    key = (torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0, slot)
-    need = _ln_ws_floats(rows, cols)
-    w = _LN_WS_BUF.get(key)
-    if w is None or w.numel() < need:
-        w = _LN_WS_BUF[key] = torch.empty(need, device=dev, dtype=F32)
-    return w
+    """Column-partial workspace of a LayerNorm backward (a pair kernel's two LayerNorms take slots
+    0 and 1).  Its size (ste_layernorm_bwd_ws_floats) stops growing once rows reach the kernel's
+    block count, so batches padded to different lengths share one buffer instead of one each."""
+    return stream_ws(dev, _ln_ws_floats(rows, cols), ("ln", slot))
 
 
 def _ln_bwd_struct(dy, x, mean, rstd, gamma, beta=None, dx=None, dxb=None, dres=None, dgamma=None, dbeta=None,

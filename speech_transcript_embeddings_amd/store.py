@@ -60,6 +60,40 @@ class Slot:
     shape: tuple
     segment: str
 
+    @property
+    def has_grad(self) -> bool:
+        """The parameter receives gradients: it lies in the prefix the gradient buffer, the Adam
+        moments and the fused optimizer cover."""
+        return self.segment in ("enc", "head")
+
+
+@dataclass(frozen=True)
+class Form:
+    """A derived operand form of a weight (or of an adjacent fused group), cached by ParamStore._form."""
+    source: str             # "shadow" (bf16 W), "master" (fp32 W), or "wt": built from wt(), rebuilt whenever that is
+    build: object           # (source matrix, previous value or None) -> value, written over the previous one
+    prebuilt: bool = False  # refresh_transposes[_in] rebuild it right after an optimizer step
+
+
+def _twice(wt, old):
+    n, k = wt.shape
+    dst = old if old is not None else torch.empty((n, 2 * k), device=wt.device, dtype=wt.dtype)
+    ops.copy2d(dst[:, :k], wt)
+    ops.copy2d(dst[:, k:], wt)
+    return dst
+
+
+def _mx8(src, old):
+    return ops.mx8_quant(src, *(old or (None, None)))
+
+
+# the public accessors of the same names document each form; a new operand form is one more row
+FORMS = {"wt": Form("shadow", lambda w, old: ops.transpose16(w, old), prebuilt=True),
+         "w2": Form("master", lambda p, old: ops.split_bf16(p, 2, 0, old), prebuilt=True),
+         "wt2": Form("wt", _twice),
+         "wq": Form("shadow", _mx8),
+         "wtq": Form("wt", _mx8)}
+
 
 class ParamStore:
     def __init__(self, model: torch.nn.Module, device, has_grad: set[str]):
@@ -122,14 +156,10 @@ class ParamStore:
             params[n] = newp
         self.params = params
         self._versions = {}
-        self._wt = {}          # (name, count) -> (Wᵀ bf16, param versions, opt_epoch) (see wt())
-        self._wq = {}          # (name, count) -> ((W e4m3, E8M0 scales), versions, opt_epoch) (see wq())
-        self._wtq = {}         # (name, count) -> ((Wᵀ e4m3, E8M0 scales), the wt() tensor, its rebuild stamp)
-        self._w2 = {}          # (name, count) -> ([W | W] bf16 [out, 2·in], versions, opt_epoch) (see w2())
-        self._wt2 = {}         # (name, count) -> ([Wᵀ | Wᵀ], the wt() tensor, its rebuild stamp) (see wt2())
-        self._wt_stamp = {}    # (name, count) -> number of wt() rebuilds (wt2 follows them)
+        self._cache = {form: {} for form in FORMS}   # form -> (name, count) -> (value, token, builds), see _form()
+        self._members = {}     # (name, count) -> names of the parameters in that fused group
         self.opt_epoch = 0     # fused optimizer steps so far (each refreshes the shadow of every trained weight)
-        self._prebuilt = None  # (event, stream, streams that waited): Wᵀ rebuilt by refresh_transposes
+        self._prebuilt = None  # (event, stream, streams that waited): forms rebuilt by refresh_transposes
         self.sync_shadow(force=True)
 
     # ------------------------------------------------------------------ views
@@ -145,7 +175,7 @@ class ParamStore:
 
     def g(self, name):
         s = self.slots[name]
-        if s.segment not in ("enc", "head"):
+        if not s.has_grad:
             return None
         return self.grad[s.offset:s.offset + s.numel].view(s.shape)
 
@@ -158,80 +188,59 @@ class ParamStore:
         if which == "p":
             base = self.master[s.offset:s.offset + n]
             return base.view(s.shape[0] * count, *s.shape[1:]) if len(s.shape) > 1 else base
-        if s.segment not in ("enc", "head"):
+        if not s.has_grad:
             return None
         base = self.grad[s.offset:s.offset + n]
         return base.view(s.shape[0] * count, *s.shape[1:]) if len(s.shape) > 1 else base
 
-    def _group_versions(self, name, count):
-        s = self.slots[name]
-        if count == 1:
-            names = [name]
+    # ------------------------------------------------- derived operand forms
+    def _token(self, name, count):
+        """What a form built from the shadow or the master was built against: the _version of every
+        parameter of the group (it moves on a write outside the optimizer) and, for a weight that
+        receives gradients, opt_epoch (the fused optimizer rewrites the shadow without it)."""
+        names = self._members.get((name, count))
+        if names is None:
+            s = self.slots[name]
+            names = self._members[name, count] = (name,) if count == 1 else tuple(
+                n for n, t in self.slots.items() if s.offset <= t.offset < s.offset + s.numel * count)
+        return tuple(self.params[n]._version for n in names), self.opt_epoch if self.slots[name].has_grad else None
+
+    def _form(self, form, name, count):
+        """The cache entry (value, token, builds) of one FORMS row for the weight `name` (count > 1:
+        the adjacent fused group starting there), rebuilt first if it is stale.  An entry is valid
+        while its token is the current one: _token() for a form built from the shadow or the
+        master, the number of wt() builds for a form built from wt().  A rebuild writes into the
+        entry's buffers.  refresh_transposes may still be writing a prebuilt form's buffer on its
+        stream, so before that buffer is returned or overwritten the current stream waits for it."""
+        f = FORMS[form]
+        if f.source == "wt":
+            src, _, token = self._form("wt", name, count)
         else:
-            names = [n for n, t in self.slots.items() if s.offset <= t.offset < s.offset + s.numel * count]
-        return tuple(self.params[n]._version for n in names), s.segment in ("enc", "head")
+            token = self._token(name, count)
+        ent = self._cache[form].get((name, count))
+        if ent is not None:
+            if f.prebuilt:
+                self._wait_prebuilt()
+            if ent[1] == token:
+                return ent
+        if f.source != "wt":
+            src = self.fused(name, count, "w" if f.source == "shadow" else "p").flatten(1)   # conv weights [out,in,1]
+        old, builds = (ent[0], ent[2]) if ent is not None else (None, 0)
+        ent = self._cache[form][name, count] = (f.build(src, old), token, builds + 1)
+        return ent
 
-    def wq(self, name: str, count: int = 1):
-        """W as MX-fp8 (e4m3 [out, in] + E8M0 scales [out, in/32]), the B operand of the MX-fp8
-        forward GEMMs (model fp8_gemm=True, BASELINE config 5).  Quantised from the bf16 shadow
-        and cached with wt()'s invalidation rules (optimizer step for trained weights, _version
-        for writes outside it)."""
-        key = (name, count)
-        versions, trained = self._group_versions(name, count)
-        ent = self._wq.get(key)
-        if ent is not None and ent[1] == versions and (not trained or ent[2] == self.opt_epoch):
-            return ent[0]
-        src = self.fused(name, count, "w") if count > 1 else self.w(name)
-        q = ops.mx8_quant(src, *(ent[0] if ent is not None else (None, None)))
-        self._wq[key] = (q, versions, self.opt_epoch)
-        return q
+    def _wait_prebuilt(self):
+        if self._prebuilt is None:
+            return
+        ev, stream, waited = self._prebuilt
+        cur = torch.cuda.current_stream(self.device)
+        if cur.cuda_stream != stream.cuda_stream and cur.cuda_stream not in waited:
+            cur.wait_event(ev)
+            waited.add(cur.cuda_stream)
 
-    def wtq(self, name: str, count: int = 1):
-        """Wᵀ as MX-fp8 (e4m3 [in, out] + E8M0 scales [in, out/32], blocks of 32 along `out`): the B
-        operand of the opt-in MX-fp8 input-gradient GEMMs dX = dY·W (engine.fp8_bwd).  Quantised
-        from wt() and rebuilt whenever wt() rebuilds its transpose."""
-        key = (name, count)
-        wt = self.wt(name, count)
-        ent = self._wtq.get(key)
-        if ent is not None and ent[1] is wt and ent[2] == self._wt_stamp.get(key):
-            return ent[0]
-        q = ops.mx8_quant(wt, *(ent[0] if ent is not None else (None, None)))
-        self._wtq[key] = (q, wt, self._wt_stamp.get(key))
-        return q
-
-    def w2(self, name: str, count: int = 1):
-        """W as [W_bf16 | W_bf16] [out, 2·in] (the B operand of ops.linear_x2: the text encoder's
-        precise forward, activations split hi | lo against the bf16 weight twice).  Built from the
-        fp32 master; cached with wt()'s invalidation rules; refresh_transposes rebuilds the trained
-        ones after an optimizer step."""
-        key = (name, count)
-        versions, trained = self._group_versions(name, count)
-        ent = self._w2.get(key)
-        if ent is not None and ent[1] == versions and (not trained or ent[2] == self.opt_epoch):
-            self._wait_prebuilt()
-            return ent[0]
-        s = self.slots[name]
-        src = self.master[s.offset:s.offset + s.numel * count].view(s.shape[0] * count, -1)
-        dst = ent[0] if ent is not None else None
-        if dst is not None:
-            self._wait_prebuilt()
-        dst = ops.split_bf16(src, 2, 0, dst)
-        self._w2[key] = (dst, versions, self.opt_epoch)
-        return dst
-
-    def wt2(self, name: str, count: int = 1):
-        """[Wᵀ | Wᵀ] bf16 [in, 2·out]: the KC operand of a dX GEMM over a [dy_hi | dy_lo] split image
-        (dy to ~fp32 against the bf16 weight).  Rebuilt from wt() whenever that is."""
-        wt = self.wt(name, count)
-        ent = self._wt2.get((name, count))
-        if ent is not None and ent[1] is wt and ent[2] == self._wt_stamp.get((name, count)):
-            return ent[0]
-        n, k = wt.shape
-        dst = ent[0] if ent is not None else torch.empty((n, 2 * k), device=wt.device, dtype=wt.dtype)
-        ops.copy2d(dst[:, :k], wt)
-        ops.copy2d(dst[:, k:], wt)
-        self._wt2[(name, count)] = (dst, wt, self._wt_stamp.get((name, count)))
-        return dst
+    def cached(self, form: str) -> int:
+        """How many (name, count) entries of a form ('wt', 'w2', 'wt2', 'wq', 'wtq') are cached."""
+        return len(self._cache[form])
 
     def wt(self, name: str, count: int = 1):
         """Wᵀ as a contiguous bf16 [in, out] matrix (the KC operand of dX = dY·W; `count` > 1:
@@ -239,28 +248,39 @@ class ParamStore:
         bf16 shadow by the transpose kernel and cached; rebuilt when the shadow changed: after
         a fused optimizer step for weights that receive gradients, or when a parameter was
         written outside the optimizer (its _version moved)."""
-        key = (name, count)
-        s = self.slots[name]
-        names = [name] if count == 1 else None
-        if names is None:
-            first = s.offset
-            names = [n for n, t in self.slots.items() if first <= t.offset < first + s.numel * count]
-        versions = tuple(self.params[n]._version for n in names)
-        trained = s.segment in ("enc", "head")
-        ent = self._wt.get(key)
-        if ent is not None and ent[1] == versions and (not trained or ent[2] == self.opt_epoch):
-            self._wait_prebuilt()
-            return ent[0]
-        src = self.fused(name, count, "w") if count > 1 else self.w(name)
-        dst = ent[0] if ent is not None else None
-        if dst is not None:
-            # the side stream's refresh_transposes may still be writing this buffer: rebuilding
-            # it on this stream without the wait would race with that write
-            self._wait_prebuilt()
-        dst = ops.transpose16(src, dst)
-        self._wt[key] = (dst, versions, self.opt_epoch)
-        self._wt_stamp[key] = self._wt_stamp.get(key, 0) + 1
-        return dst
+        return self._form("wt", name, count)[0]
+
+    def w2(self, name: str, count: int = 1):
+        """W as [W_bf16 | W_bf16] [out, 2·in] (the B operand of ops.linear_x2: the text encoder's
+        precise forward, activations split hi | lo against the bf16 weight twice).  Built from the
+        fp32 master; cached with wt()'s invalidation rules; refresh_transposes rebuilds the trained
+        ones after an optimizer step."""
+        return self._form("w2", name, count)[0]
+
+    def wt2(self, name: str, count: int = 1):
+        """[Wᵀ | Wᵀ] bf16 [in, 2·out]: the KC operand of a dX GEMM over a [dy_hi | dy_lo] split image
+        (dy to ~fp32 against the bf16 weight).  Rebuilt from wt() whenever that is."""
+        return self._form("wt2", name, count)[0]
+
+    def wq(self, name: str, count: int = 1):
+        """W as MX-fp8 (e4m3 [out, in] + E8M0 scales [out, in/32]), the B operand of the MX-fp8
+        forward GEMMs (model fp8_gemm=True, BASELINE config 5).  Quantised from the bf16 shadow
+        and cached with wt()'s invalidation rules (optimizer step for trained weights, _version
+        for writes outside it)."""
+        return self._form("wq", name, count)[0]
+
+    def wtq(self, name: str, count: int = 1):
+        """Wᵀ as MX-fp8 (e4m3 [in, out] + E8M0 scales [in, out/32], blocks of 32 along `out`): the B
+        operand of the opt-in MX-fp8 input-gradient GEMMs dX = dY·W (engine.fp8_bwd).  Quantised
+        from wt() and rebuilt whenever wt() rebuilds its transpose."""
+        return self._form("wtq", name, count)[0]
+
+    def _stale_prebuilt(self, inside=lambda slot: True):
+        """(form, name, count) of every cached prebuilt form of a weight the fused optimizer has
+        updated since the form was built."""
+        return [(form, *key) for form, f in FORMS.items() if f.prebuilt
+                for key, ent in self._cache[form].items()
+                if self.slots[key[0]].has_grad and ent[1][1] != self.opt_epoch and inside(self.slots[key[0]])]
 
     def refresh_transposes(self, stream):
         """Rebuild on `stream` every cached Wᵀ of a weight the fused optimizer just updated
@@ -269,20 +289,14 @@ class ParamStore:
         one of them from wt() first waits for this work (one event)."""
         if stream is None or self.device.type != "cuda":
             return
-        stale = [k for k, ent in self._wt.items()
-                 if ent[2] != self.opt_epoch and self.slots[k[0]].segment in ("enc", "head")]
-        stale2 = [k for k, ent in self._w2.items()
-                  if ent[2] != self.opt_epoch and self.slots[k[0]].segment in ("enc", "head")]
-        if not stale and not stale2:
+        stale = self._stale_prebuilt()
+        if not stale:
             return
-        cur = torch.cuda.current_stream(self.device)
-        stream.wait_stream(cur)               # the optimizer's shadow writes
+        stream.wait_stream(torch.cuda.current_stream(self.device))   # the optimizer's shadow writes
         self._prebuilt = None                 # the rebuilds below must not wait on the previous event
         with torch.cuda.stream(stream):
-            for name, count in stale:
-                self.wt(name, count)
-            for name, count in stale2:
-                self.w2(name, count)
+            for key in stale:
+                self._form(*key)
             ev = torch.cuda.Event()
             ev.record(stream)
         self._prebuilt = (ev, stream, set())
@@ -295,24 +309,11 @@ class ParamStore:
         if self.device.type != "cuda":
             return
         self._prebuilt = None
-        inside = lambda k: any(a <= self.slots[k[0]].offset < b for a, b in runs)  # noqa: E731
-        for cache, build in ((self._wt, self.wt), (self._w2, self.w2)):
-            for k in [k for k, ent in cache.items() if ent[2] != self.opt_epoch
-                      and self.slots[k[0]].segment in ("enc", "head") and inside(k)]:
-                build(*k)
-
-    def _wait_prebuilt(self):
-        pb = getattr(self, "_prebuilt", None)
-        if pb is None:
-            return
-        ev, stream, waited = pb
-        cur = torch.cuda.current_stream(self.device)
-        if cur.cuda_stream != stream.cuda_stream and cur.cuda_stream not in waited:
-            cur.wait_event(ev)
-            waited.add(cur.cuda_stream)
+        for key in self._stale_prebuilt(lambda slot: any(a <= slot.offset < b for a, b in runs)):
+            self._form(*key)
 
     def trainable_layer(self, name: str) -> bool:
-        return self.slots[name].segment in ("enc", "head")
+        return self.slots[name].has_grad
 
     # ----------------------------------------------------------------- shadow
     def sync_shadow(self, force=False):
@@ -337,15 +338,10 @@ class ParamStore:
     def attach_grads(self):
         """Point .grad of every gradient-receiving parameter at its slice of the flat buffer.
         Returns True if the buffer must be zeroed first (grads were reset to None)."""
-        reset = False
-        for n, s in self.slots.items():
-            if s.segment in ("enc", "head"):
-                p = self.params[n]
-                if p.grad is None:
-                    reset = True
+        names = [n for n, s in self.slots.items() if s.has_grad]
+        reset = any(self.params[n].grad is None for n in names)
         if reset:
             self.grad.zero_()
-            for n, s in self.slots.items():
-                if s.segment in ("enc", "head"):
-                    self.params[n].grad = self.grad[s.offset:s.offset + s.numel].view(s.shape)
+            for n in names:
+                self.params[n].grad = self.g(n)
         return reset

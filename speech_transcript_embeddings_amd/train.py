@@ -114,7 +114,7 @@ class FusedAdamW:
             ids = []
             for n in names:
                 s = st.slots[n]
-                if self.t > 0 and s.segment in ("enc", "head"):
+                if self.t > 0 and s.has_grad:
                     sl = slice(s.offset, s.offset + s.numel)
                     state[idx] = {"step": torch.tensor(float(self.t), dtype=F32),
                                   "exp_avg": self.exp_avg[sl].view(s.shape).clone(),
@@ -145,7 +145,7 @@ class FusedAdamW:
                 if ps is None:
                     continue
                 s = st.slots[n]
-                if s.segment not in ("enc", "head"):
+                if not s.has_grad:
                     continue  # a parameter the HIP backward never produces a gradient for
                 sl = slice(s.offset, s.offset + s.numel)
                 self.exp_avg[sl].copy_(ps["exp_avg"].reshape(-1).to(self.exp_avg.device, F32))
@@ -275,7 +275,7 @@ class GradSync:
         self._agreed = False   # unconfigured: the capacity was agreed for the current step
         self._pending_cap = None   # start_capacity()'s (event, pinned host value, device value)
         self._cap_stream = None
-        grad_slots = [sl for sl in store.slots.values() if sl.segment in ("enc", "head")]
+        grad_slots = [sl for sl in store.slots.values() if sl.has_grad]
 
         ordered = sorted(grad_slots, key=lambda x: x.offset)
 

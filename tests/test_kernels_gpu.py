@@ -97,6 +97,79 @@ def test_dx_through_cached_transpose():
     assert torch.equal(st.wt(frozen), st.w(frozen).t())
 
 
+@pytest.mark.parametrize("overlap_optimizer", [False, True])
+def test_store_operand_forms(overlap_optimizer):
+    """Every cached weight operand of ParamStore (wt, w2, wt2, wq, wtq) equals its definition bit
+    for bit, is reused while nothing changed, and follows optimizer steps (trained weights: rebuilt
+    in place; frozen ones: the same objects) and writes outside the optimizer.  The default
+    TrainStep rebuilds wt / w2 on the side stream (refresh_transposes), overlap_optimizer=True per
+    block on the optimizer stream (refresh_transposes_in); wt2 / wtq follow wt and are taken here
+    before wt is, so their own dependence on it is what rebuilds them."""
+    import json
+    from conftest import GOLDEN
+    from test_model_gpu import mini_model
+    from speech_transcript_embeddings_amd import ops
+    from speech_transcript_embeddings_amd.train import TrainStep, synthetic_batch
+    meta = json.loads((GOLDEN / "model_golden_noalign.json").read_text())
+    model = mini_model(meta)
+    st = model.store
+    trained = ("audio_encoder.encoder.layers.1.ffn1.intermediate_dense.weight", 1)
+    frozen = ("audio_encoder.encoder.layers.0.ffn1.intermediate_dense.weight", 1)
+    qkv = ("audio_encoder.encoder.layers.1.self_attn.linear_q.weight", 3)   # fused Q|K|V, trained
+    assert st.slots[frozen[0]].segment == "frozen"
+    assert st.slots[trained[0]].segment == st.slots[qkv[0]].segment == "enc"
+    FOLLOWERS, PRIMARY = ("wt2", "wtq"), ("wt", "w2", "wq")
+
+    def parts(v):   # the MX forms are (e4m3 bytes, E8M0 scales) pairs
+        return v if isinstance(v, tuple) else (v,)
+
+    def definition(form, key):
+        w = st.fused(*key, "w")
+        assert key[1] > 1 or (w.data_ptr() == st.w(key[0]).data_ptr() and w.shape == st.w(key[0]).shape)
+        wt = w.t().contiguous()
+        return {"wt": lambda: (wt,), "w2": lambda: (torch.cat([w, w], 1),), "wt2": lambda: (torch.cat([wt, wt], 1),),
+                "wq": lambda: ops.mx8_quant(w), "wtq": lambda: ops.mx8_quant(wt)}[form]()
+
+    def check(form, key):
+        got = parts(getattr(st, form)(*key))
+        want = definition(form, key)
+        assert len(got) == len(want)
+        for g, d in zip(got, want):
+            assert g.shape == d.shape and torch.equal(g, d), (form, key)
+        return got
+
+    st.sync_shadow()
+    before = {}
+    for key in (trained, frozen, qkv):
+        for form in PRIMARY + FOLLOWERS:
+            got = check(form, key)
+            again = parts(getattr(st, form)(*key))
+            assert all(a is g for a, g in zip(again, got)), (form, key)   # reuse
+            before[form, key] = (got, [g.clone() for g in got])
+
+    step = TrainStep(model, lr=1e-2, warmup=1, total_steps=10, overlap_optimizer=overlap_optimizer)
+    data = synthetic_batch(2, 16000, 12, vocab=meta["mini"]["text"]["vocab_size"], seed=1)
+    step(*data)
+    step(*data)
+    step.sync()
+    st.sync_shadow()
+    for form in FOLLOWERS + PRIMARY:    # followers first: no wt() of this test's between before and after
+        got = parts(getattr(st, form)(*frozen))
+        assert all(g is b for g, b in zip(got, before[form, frozen][0])), form   # frozen: built once
+        for key in (trained, qkv):
+            got = check(form, key)      # follows the optimizer ...
+            old, old_values = before[form, key]
+            assert not torch.equal(got[0], old_values[0]), (form, key)
+            assert [g.data_ptr() for g in got] == [o.data_ptr() for o in old], (form, key)   # ... in place
+
+    with torch.no_grad():   # a write outside the optimizer (e.g. load_state_dict)
+        model.get_parameter(frozen[0]).mul_(2.0)
+    st.sync_shadow()
+    assert not torch.equal(st.w(frozen[0]), before["wt", frozen][1][0].t())
+    for form in FOLLOWERS + PRIMARY:
+        check(form, frozen)
+
+
 @pytest.mark.parametrize("M,N,K,ws_mb", [(4096, 1024, 31936, 80),   # c2 FFN intermediate dW: S=4, 3 leftover K-tiles on slabs 0-2
                                          (1024, 1024, 31936, 80),   # c2 O-proj dW: S=16, Kc=31, 3 leftover K-tiles
                                          (1024, 1024, 15968, 80),   # c3 (b=32) O-proj dW: S=16, ragged 32-row tail

@@ -323,7 +323,7 @@ def test_fp8_gemm_matches_oracle():
     for k, v in errs.items():
         assert v < 5e-2, (k, v)
     # the MX-fp8 path really ran: the cached quantised weights exist for every Conformer Linear
-    n_q = len(model.store._wq)  # FFN1 in/out, QKV, O, pw1, pw2, FFN2 in/out per layer
+    n_q = model.store.cached("wq")  # FFN1 in/out, QKV, O, pw1, pw2, FFN2 in/out per layer
     assert n_q == 8 * meta["mini"]["audio"]["num_hidden_layers"], n_q
     params = dict(model.named_parameters())
     worst = []
