@@ -596,6 +596,44 @@ int ste_w2v_wave_norm(const float* wave, int64_t ldw, const int32_t* lengths, in
  * backward of an output dropout + row mask, in place on a contiguous fp32 [M, N]. */
 int ste_w2v_drop_rows(float* x, int M, int N, float p, uint64_t seed, const float* maskf, void* stream);
 
+/* ---- layer-norm feature encoder (feat_extract_norm="layer", conv_bias=True: XLSR-53, XLS-R,
+ * the -lv60 family): Wav2Vec2LayerNormConvLayer (tf:…/modeling_wav2vec2.py:275-299) after EVERY
+ * conv layer: conv + bias, LayerNorm over the C channels of each frame (biased variance, eps),
+ * GELU.  Row kernels, one wave per frame; mean/rstd fp32 [rows] are kept for the backward.
+ * Every column sum goes through per-block partial slabs in `work`, summed in block order:
+ * deterministic, no atomics.
+ *
+ * Layer 0 (replaces :290-297 for C_in = 1): h bf16 [B*T0, C] = gelu(LN_c(bias[c] + Σ_j w0[c, j]·
+ * wave[b, S0·t + j])·γ + β); the pre-norm activation never reaches memory (the backward
+ * recomputes it from the samples).  K0 <= 16, S0 <= 8, S0·(T0-1) + K0 <= N <= ldw as
+ * ste_w2v_conv0_fwd; C % 4 == 0, C <= 512 (the taps of a lane's channels live in registers). */
+int ste_w2v_conv0_ln_fwd(const float* wave, int64_t ldw, const float* w0, const float* bias, const float* gamma,
+                         const float* beta, int B, int N, int T0, int C, int K0, int S0, float eps, void* h,
+                         float* mean, float* rstd, void* stream);
+/* Backward of the above (autograd of :290-297) given dh = dL/dh fp32 [B*T0, C]:
+ * g = dh·gelu'(x̂γ + β), dy = LN'(g); dgamma += Σ g·x̂, dbeta += Σ g, dbias += Σ dy,
+ * dw0[c, j] += Σ dy·wave[b, S0·t + j]; each output may be NULL.
+ * work: ste_w2v_conv0_ln_work(B, T0, C, K0) floats (0: bad shape). */
+int64_t ste_w2v_conv0_ln_work(int B, int T0, int C, int K0);
+int ste_w2v_conv0_ln_bwd(const float* dh, const float* wave, int64_t ldw, const float* mean, const float* rstd,
+                         const float* w0, const float* bias, const float* gamma, const float* beta, int B, int N,
+                         int T0, int C, int K0, int S0, float* dgamma, float* dbeta, float* dbias, float* dw0,
+                         float* work, int64_t work_floats, void* stream);
+/* Layers >= 1 (replaces :293-297 after the strided-view GEMM with the conv bias in its epilogue):
+ * h [rows, C] = gelu(LN_c(z)·γ + β) from z bf16 [rows, C]; h is fp32 if h_f32 (the last layer, read
+ * by feature_projection.layer_norm) else bf16.  C % 4 == 0, C <= 1024, rows < 2^31. */
+int ste_w2v_ln_gelu_fwd(const void* z, const float* gamma, const float* beta, int64_t rows, int C, float eps, void* h,
+                        int h_f32, float* mean, float* rstd, void* stream);
+/* Backward of the above: dh [rows, C] fp32, or bf16 if dh_bf16 (both forms ste_w2v_conv_fold
+ * emits); dz bf16 [rows, C] = LN'(dh·gelu'(x̂γ + β)) — the dY operand of the layer's dW / dX GEMMs;
+ * dgamma += Σ g·x̂, dbeta += Σ g, dbias += Σ dz (the conv bias gradient, summed before dz is
+ * rounded); each sum may be NULL, and with all three NULL no work is needed.
+ * work: ste_w2v_ln_gelu_work(rows, C) floats (0: bad shape). */
+int64_t ste_w2v_ln_gelu_work(int64_t rows, int C);
+int ste_w2v_ln_gelu_bwd(const void* dh, int dh_bf16, const void* z, const float* mean, const float* rstd,
+                        const float* gamma, const float* beta, int64_t rows, int C, void* dz, float* dgamma,
+                        float* dbeta, float* dbias, float* work, int64_t work_floats, void* stream);
+
 const char* ste_version(void);
 
 #ifdef __cplusplus

@@ -242,6 +242,17 @@ _SIGS = {
                                    c_void_p, c_void_p]),
     "ste_w2v_wave_norm": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p]),
     "ste_w2v_drop_rows": (c_int, [c_void_p, c_int, c_int, c_float, c_uint64, c_void_p, c_void_p]),
+    "ste_w2v_conv0_ln_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                     c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ste_w2v_conv0_ln_work": (c_int64, [c_int, c_int, c_int, c_int]),
+    "ste_w2v_conv0_ln_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ste_w2v_ln_gelu_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_void_p]),
+    "ste_w2v_ln_gelu_work": (c_int64, [c_int64, c_int]),
+    "ste_w2v_ln_gelu_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "ste_version": (C.c_char_p, []),
 }
 

@@ -704,3 +704,591 @@ extern "C" int ste_w2v_drop_rows(float* x, int M, int N, float p, uint64_t seed,
   STE_CHECK_LAUNCH();
   return 0;
 }
+
+// ====================================================================================
+// Layer-norm feature encoder (feat_extract_norm="layer", conv_bias=True: XLS-R / XLSR-53 / lv60)
+//   tf:…/modeling_wav2vec2.py:275-299 Wav2Vec2LayerNormConvLayer: conv + bias, LayerNorm over the
+//   C channels of every frame (eps 1e-5), GELU — after EVERY conv layer.
+// Row kernels, HBM-bound: one wave per frame, a lane holds NCH quads of channels in registers
+// (quad i at 4·(lane + 64·i), or for C % 8 == 0 in the LayerNorm + GELU kernels 8 adjacent channels
+// per lane, see qchan); statistics by DPP/permlane wave sums (two-pass variance);
+// γ/β (and conv0's taps and bias) are loaded once per wave and reused over its frames.  Column
+// sums (dγ, dβ, dbias, dw0): per-lane register accumulators over the wave's frames, the block's
+// four waves added in wave order in LDS, one partial slab per block, slabs summed in block
+// order by slab_sum_kernel / seg_sum_kernel: no atomics, run-to-run deterministic.
+namespace {
+
+constexpr int LN_WAVES = NT / STE_WAVE;
+constexpr int LN_MAX_BLOCKS = 2048;   // row kernels: grid cap (rows are grid-strided per wave)
+constexpr int C0_TT = 64;             // conv0: frames per block (16 per wave)
+constexpr int C0_MAX_BLOCKS = 1024;   // conv0 backward: about this many partial slabs
+
+STE_DEV f32x4 ldg4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+// First channel of quad i of a lane.  VEC = 4: 4·(lane + 64·i).  VEC = 8 (C % 8 == 0; the bf16
+// rows are then read and written 16 B per lane): quads 2k and 2k + 1 are the two halves of the 8
+// channels at 8·(lane + 64·k).
+template <int VEC>
+STE_DEV int qchan(int i, int lane) {
+  return VEC == 8 ? 8 * (lane + 64 * (i >> 1)) + 4 * (i & 1) : 4 * (lane + 64 * i);
+}
+
+// a bf16 row <-> a lane's quads (zeros past C)
+template <int NCH, int VEC>
+STE_DEV void load_row(const bf16* __restrict__ p, int lane, int C, f32x4 (&x)[NCH]) {
+  if constexpr (VEC == 8) {
+#pragma unroll
+    for (int k = 0; k < NCH / 2; ++k) {
+      const int c = 8 * (lane + 64 * k);
+      x[2 * k] = x[2 * k + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      if (c >= C) continue;
+      const bf16x8 v = *reinterpret_cast<const bf16x8*>(p + c);
+      x[2 * k] = f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+      x[2 * k + 1] = f32x4{(float)v[4], (float)v[5], (float)v[6], (float)v[7]};
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int c = 4 * (lane + 64 * i);
+      x[i] = c < C ? load_bf16x4(p + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+}
+template <int NCH, int VEC>
+STE_DEV void store_row(bf16* __restrict__ p, int lane, int C, const f32x4 (&o)[NCH]) {
+  if constexpr (VEC == 8) {
+#pragma unroll
+    for (int k = 0; k < NCH / 2; ++k) {
+      const int c = 8 * (lane + 64 * k);
+      if (c >= C) continue;
+      const f32x4 a = o[2 * k], b = o[2 * k + 1];
+      *reinterpret_cast<bf16x8*>(p + c) =
+          bf16x8{(bf16)a[0], (bf16)a[1], (bf16)a[2], (bf16)a[3], (bf16)b[0], (bf16)b[1], (bf16)b[2], (bf16)b[3]};
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int c = 4 * (lane + 64 * i);
+      if (c < C) store_bf16x4(p + c, o[i]);
+    }
+  }
+}
+
+// mean and 1/sqrt(var + eps) of a row held as quads x[i] (quads past C hold zeros and are skipped)
+template <int NCH, int VEC = 4>
+STE_DEV void row_stats(const f32x4 (&x)[NCH], int lane, int C, float eps, float& mu, float& rs) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+    if (qchan<VEC>(i, lane) < C) s += (x[i][0] + x[i][1]) + (x[i][2] + x[i][3]);
+  mu = wave_sum(s) / (float)C;
+  float q = 0.f;
+#pragma unroll
+  for (int i = 0; i < NCH; ++i)
+    if (qchan<VEC>(i, lane) < C) {
+      const f32x4 d = x[i] - mu;
+      q += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
+    }
+  rs = 1.0f / sqrtf(wave_sum(q) / (float)C + eps);
+}
+
+// h = gelu((z - mean)·rstd·γ + β)
+template <int NCH, int VEC, bool OUT_F32>
+__global__ __launch_bounds__(NT) void ln_gelu_fwd_kernel(const bf16* __restrict__ z, const float* __restrict__ g,
+                                                         const float* __restrict__ be, int rows, int C, float eps,
+                                                         float* __restrict__ mean, float* __restrict__ rstd,
+                                                         void* __restrict__ h) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  f32x4 gc[NCH], bc[NCH];
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    const int c = qchan<VEC>(i, lane);
+    gc[i] = c < C ? ldg4(g + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    bc[i] = c < C ? ldg4(be + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  for (int row = blockIdx.x * LN_WAVES + wave; row < rows; row += gridDim.x * LN_WAVES) {
+    const int64_t e = (int64_t)row * C;
+    f32x4 x[NCH];
+    load_row<NCH, VEC>(z + e, lane, C, x);
+    float mu, rs;
+    row_stats<NCH, VEC>(x, lane, C, eps, mu, rs);
+    if (lane == 0) {
+      mean[row] = mu;
+      rstd[row] = rs;
+    }
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) x[i][q] = gelu_f((x[i][q] - mu) * rs * gc[i][q] + bc[i][q]);
+    if (OUT_F32) {
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        const int c = qchan<VEC>(i, lane);
+        if (c < C) *reinterpret_cast<f32x4*>((float*)h + e + c) = x[i];
+      }
+    } else {
+      store_row<NCH, VEC>((bf16*)h + e, lane, C, x);
+    }
+  }
+}
+
+// The four waves' column accumulators added in wave order in LDS (sacc: nacc·C floats, layout
+// [k][C]) and written as this block's slab part[blockIdx.x][nacc·C].
+template <int NCH, int NACC, int VEC>
+STE_DEV void block_colsum(const f32x4 (&acc)[NACC][NCH], int lane, int wave, int C, float* sacc,
+                          float* __restrict__ part) {
+  for (int w = 0; w < LN_WAVES; ++w) {
+    if (wave == w) {
+#pragma unroll
+      for (int k = 0; k < NACC; ++k)
+#pragma unroll
+        for (int i = 0; i < NCH; ++i) {
+          const int c = qchan<VEC>(i, lane);
+          if (c >= C) continue;
+          f32x4* p = reinterpret_cast<f32x4*>(sacc + k * C + c);
+          *p = w == 0 ? acc[k][i] : *p + acc[k][i];
+        }
+    }
+    __syncthreads();
+  }
+  float* pout = part + (int64_t)blockIdx.x * NACC * C;
+  for (int i = threadIdx.x; i < NACC * C; i += NT) pout[i] = sacc[i];
+}
+
+// g = dh·gelu'(x̂γ + β); dz = rstd·(gγ - mean_c(gγ) - x̂·mean_c(gγ·x̂)) (bf16);
+// part[block] = [Σ g·x̂ (dγ) | Σ g (dβ) | Σ dz (conv bias gradient)]
+template <int NCH, int VEC, bool DH_BF16>
+__global__ __launch_bounds__(NT) void ln_gelu_bwd_kernel(const void* __restrict__ dh, const bf16* __restrict__ z,
+                                                         const float* __restrict__ mean,
+                                                         const float* __restrict__ rstd, const float* __restrict__ g,
+                                                         const float* __restrict__ be, int rows, int C,
+                                                         bf16* __restrict__ dz, float* __restrict__ part) {
+  extern __shared__ float sacc[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float invC = 1.0f / (float)C;
+  f32x4 gc[NCH], bc[NCH], acc[3][NCH];
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    const int c = qchan<VEC>(i, lane);
+    gc[i] = c < C ? ldg4(g + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    bc[i] = c < C ? ldg4(be + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  for (int row = blockIdx.x * LN_WAVES + wave; row < rows; row += gridDim.x * LN_WAVES) {
+    const int64_t e = (int64_t)row * C;
+    const float mu = mean[row], rs = rstd[row];
+    f32x4 xh[NCH], gy[NCH];
+    load_row<NCH, VEC>(z + e, lane, C, xh);
+    if (DH_BF16) {
+      load_row<NCH, VEC>((const bf16*)dh + e, lane, C, gy);
+    } else {
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        const int c = qchan<VEC>(i, lane);
+        gy[i] = c < C ? ldg4((const float*)dh + e + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+    }
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      if (qchan<VEC>(i, lane) >= C) {   // x̂ of a quad past C is not 0 ((0 - mean)·rstd): keep it out of the sums
+        xh[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        continue;
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float xq = (xh[i][q] - mu) * rs;
+        const float gg = gy[i][q] * gelu_d(xq * gc[i][q] + bc[i][q]);
+        acc[0][i][q] += gg * xq;
+        acc[1][i][q] += gg;
+        xh[i][q] = xq;
+        gy[i][q] = gg * gc[i][q];
+        s1 += gy[i][q];
+        s2 += gy[i][q] * xq;
+      }
+    }
+    s1 = wave_sum(s1) * invC;
+    s2 = wave_sum(s2) * invC;
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      if (qchan<VEC>(i, lane) >= C) continue;
+      gy[i] = rs * (gy[i] - s1 - xh[i] * s2);
+      acc[2][i] += gy[i];
+    }
+    store_row<NCH, VEC>(dz + e, lane, C, gy);
+  }
+  if (part) block_colsum<NCH, 3, VEC>(acc, lane, wave, C, sacc, part);
+}
+
+// conv0 + bias + LayerNorm(C) + GELU of C0_TT frames of one clip: the block's samples staged
+// once in LDS (every lane reads the same tap sample: a broadcast), taps in registers.
+// KT: compiled tap count (K0 <= KT).
+template <int NCH, int KT>
+__global__ __launch_bounds__(NT) void conv0_ln_fwd_kernel(const float* __restrict__ x, int64_t ldx,
+                                                          const float* __restrict__ w, const float* __restrict__ bias,
+                                                          const float* __restrict__ g, const float* __restrict__ be,
+                                                          int T0, int C, int K0, int S, float eps,
+                                                          float* __restrict__ mean, float* __restrict__ rstd,
+                                                          bf16* __restrict__ h) {
+  __shared__ float sx[(C0_TT - 1) * 8 + KMAX0];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.y, t0 = blockIdx.x * C0_TT;
+  const int nt = min(C0_TT, T0 - t0);
+  const int nsamp = S * (nt - 1) + K0;
+  const float* xb = x + (int64_t)b * ldx + (int64_t)S * t0;
+  for (int i = threadIdx.x; i < nsamp; i += NT) sx[i] = xb[i];
+  float wk[NCH][4][KT];
+  f32x4 bi[NCH], gc[NCH], bc[NCH];
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    const int c = 4 * (lane + 64 * i);
+    const bool ok = c < C;
+    bi[i] = ok ? ldg4(bias + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    gc[i] = ok ? ldg4(g + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    bc[i] = ok ? ldg4(be + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int j = 0; j < KT; ++j) wk[i][q][j] = (ok && j < K0) ? w[(c + q) * K0 + j] : 0.f;
+  }
+  __syncthreads();
+  for (int t = wave; t < nt; t += LN_WAVES) {
+    const float* xs = sx + S * t;
+    float xv[KT];
+#pragma unroll
+    for (int j = 0; j < KT; ++j) xv[j] = j < K0 ? xs[j] : 0.f;
+    f32x4 y[NCH];
+#pragma unroll
+    for (int i = 0; i < NCH; ++i)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        float a = bi[i][q];
+#pragma unroll
+        for (int j = 0; j < KT; ++j) a = fmaf(wk[i][q][j], xv[j], a);
+        y[i][q] = a;
+      }
+    float mu, rs;
+    row_stats<NCH>(y, lane, C, eps, mu, rs);
+    const int64_t row = (int64_t)b * T0 + t0 + t;
+    if (lane == 0) {
+      mean[row] = mu;
+      rstd[row] = rs;
+    }
+#pragma unroll
+    for (int i = 0; i < NCH; ++i) {
+      const int c = 4 * (lane + 64 * i);
+      if (c >= C) continue;
+      f32x4 o;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) o[q] = gelu_f((y[i][q] - mu) * rs * gc[i][q] + bc[i][q]);
+      store_bf16x4(h + row * C + c, o);
+    }
+  }
+}
+
+// Backward of the above over a chunk of `tchunk` frames of one clip: y recomputed from the
+// samples, dy = LN'(dh·gelu'), per-lane sums of dy·x[S·t + j] (dw0), g·x̂ (dγ), g (dβ), dy (dbias).
+// part[block] = [dw0 C·K0 | dγ C | dβ C | dbias C]; sacc: C·(K0 + 3) floats of LDS.
+template <int NCH, int KT>
+__global__ __launch_bounds__(NT) void conv0_ln_bwd_kernel(const float* __restrict__ dh, const float* __restrict__ x,
+                                                          int64_t ldx, const float* __restrict__ mean,
+                                                          const float* __restrict__ rstd, const float* __restrict__ w,
+                                                          const float* __restrict__ bias, const float* __restrict__ g,
+                                                          const float* __restrict__ be, int T0, int C, int K0, int S,
+                                                          int tchunk, float* __restrict__ part) {
+  __shared__ float sx[(C0_TT - 1) * 8 + KMAX0];
+  extern __shared__ float sacc[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.y, tb = blockIdx.x * tchunk, te = min(T0, tb + tchunk);
+  const float invC = 1.0f / (float)C;
+  float wk[NCH][4][KT], aw[NCH][4][KT];
+  f32x4 bi[NCH], gc[NCH], bc[NCH], acc[3][NCH];
+#pragma unroll
+  for (int i = 0; i < NCH; ++i) {
+    const int c = 4 * (lane + 64 * i);
+    const bool ok = c < C;
+    bi[i] = ok ? ldg4(bias + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    gc[i] = ok ? ldg4(g + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+    bc[i] = ok ? ldg4(be + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc[k][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int j = 0; j < KT; ++j) {
+        wk[i][q][j] = (ok && j < K0) ? w[(c + q) * K0 + j] : 0.f;
+        aw[i][q][j] = 0.f;
+      }
+  }
+  for (int t0 = tb; t0 < te; t0 += C0_TT) {
+    const int nt = min(C0_TT, te - t0);
+    const int nsamp = S * (nt - 1) + K0;
+    const float* xb = x + (int64_t)b * ldx + (int64_t)S * t0;
+    __syncthreads();
+    for (int i = threadIdx.x; i < nsamp; i += NT) sx[i] = xb[i];
+    __syncthreads();
+    for (int t = wave; t < nt; t += LN_WAVES) {
+      const float* xs = sx + S * t;
+      const int64_t row = (int64_t)b * T0 + t0 + t;
+      const float mu = mean[row], rs = rstd[row];
+      float xv[KT];
+#pragma unroll
+      for (int j = 0; j < KT; ++j) xv[j] = j < K0 ? xs[j] : 0.f;
+      f32x4 xh[NCH], gy[NCH];
+      float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        const int c = 4 * (lane + 64 * i);
+        xh[i] = gy[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (c >= C) continue;
+        const f32x4 d = ldg4(dh + row * C + c);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          float y = bi[i][q];
+#pragma unroll
+          for (int j = 0; j < KT; ++j) y = fmaf(wk[i][q][j], xv[j], y);
+          const float xq = (y - mu) * rs;
+          const float gg = d[q] * gelu_d(xq * gc[i][q] + bc[i][q]);
+          acc[0][i][q] += gg * xq;
+          acc[1][i][q] += gg;
+          xh[i][q] = xq;
+          gy[i][q] = gg * gc[i][q];
+          s1 += gy[i][q];
+          s2 += gy[i][q] * xq;
+        }
+      }
+      s1 = wave_sum(s1) * invC;
+      s2 = wave_sum(s2) * invC;
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        if (4 * (lane + 64 * i) >= C) continue;
+        const f32x4 dy = rs * (gy[i] - s1 - xh[i] * s2);
+        acc[2][i] += dy;
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int j = 0; j < KT; ++j) aw[i][q][j] = fmaf(dy[q], xv[j], aw[i][q][j]);
+      }
+    }
+  }
+  // the four waves' sums in wave order: dw0 [C][K0] first, then dγ | dβ | dbias
+  const int nw = C * K0;
+  __syncthreads();
+  for (int wv = 0; wv < LN_WAVES; ++wv) {
+    if (wave == wv) {
+#pragma unroll
+      for (int i = 0; i < NCH; ++i) {
+        const int c = 4 * (lane + 64 * i);
+        if (c >= C) continue;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+#pragma unroll
+          for (int j = 0; j < KT; ++j)
+            if (j < K0) {
+              float* p = sacc + (c + q) * K0 + j;
+              *p = wv == 0 ? aw[i][q][j] : *p + aw[i][q][j];
+            }
+#pragma unroll
+          for (int k = 0; k < 3; ++k) {
+            float* p = sacc + nw + k * C + c + q;
+            *p = wv == 0 ? acc[k][i][q] : *p + acc[k][i][q];
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  const int n = nw + 3 * C;
+  float* pout = part + ((int64_t)b * gridDim.x + blockIdx.x) * n;
+  for (int i = threadIdx.x; i < n; i += NT) pout[i] = sacc[i];
+}
+
+// out_k[i - lo_k] += Σ_{s < S} part[s·n + i] for the segment k = [lo_k, end_k) holding i
+// (fixed slab order; a NULL out_k skips its segment)
+struct ColSegs {
+  float* out[4];
+  int end[4];
+};
+__global__ __launch_bounds__(NT) void seg_sum_kernel(const float* __restrict__ part, int n, int S, ColSegs segs) {
+  const int i = blockIdx.x * NT + threadIdx.x;
+  if (i >= n) return;
+  int k = 0, lo = 0;
+  while (k < 3 && i >= segs.end[k]) lo = segs.end[k++];
+  if (!segs.out[k]) return;
+  float a = 0.f;
+  for (int s = 0; s < S; ++s) a += part[(int64_t)s * n + i];
+  segs.out[k][i - lo] += a;
+}
+
+// S slabs of n floats at work -> the segments' outputs; more than 32 slabs go through one level
+// of 32-slab group sums (work + S·n, ceil(S/32) slabs) first
+int seg_sum(float* work, int64_t n, int S, const ColSegs& segs, hipStream_t s) {
+  const float* src = work;
+  if (S > 32) {
+    const int S2 = (S + 31) / 32;
+    float* part2 = work + (int64_t)S * n;
+    hipLaunchKernelGGL(slab_sum_kernel<false>, dim3(grid_for(n), S2), dim3(NT), 0, s, part2, work, n, S, 32);
+    STE_CHECK_LAUNCH();
+    src = part2;
+    S = S2;
+  }
+  hipLaunchKernelGGL(seg_sum_kernel, dim3((unsigned)((n + NT - 1) / NT)), dim3(NT), 0, s, src, (int)n, S, segs);
+  STE_CHECK_LAUNCH();
+  return 0;
+}
+
+bool ln_shape_ok(int64_t rows, int C) { return rows > 0 && rows < (1ll << 31) && C > 0 && (C & 3) == 0 && C <= 1024; }
+// 8 channels per lane access (16-B bf16 loads and stores): C % 8 == 0 and 16-B aligned rows
+bool ln_vec8(int C, const void* a, const void* b) {
+  return (C & 7) == 0 && (((uintptr_t)a | (uintptr_t)b) & 15) == 0;
+}
+int ln_blocks(int64_t rows) {
+  const int64_t b = (rows + LN_WAVES - 1) / LN_WAVES;
+  return (int)(b < LN_MAX_BLOCKS ? b : LN_MAX_BLOCKS);
+}
+
+// conv0 + LayerNorm: taps live in registers, so C <= 512 (two chunks per lane)
+bool c0_shape_ok(int B, int N, int T0, int C, int K0, int S0, int64_t ldw) {
+  return B > 0 && T0 > 0 && (int64_t)B * T0 < (1ll << 31) && C > 0 && (C & 3) == 0 && C <= 512 && K0 > 0 &&
+         K0 <= KMAX0 && S0 > 0 && S0 <= 8 && ldw >= N && (int64_t)S0 * (T0 - 1) + K0 <= N && B <= 65535;
+}
+struct C0Plan {
+  int tchunk, nc0;  // frames per backward block, blocks per clip
+};
+C0Plan c0_plan(int B, int T0) {
+  C0Plan p;
+  int nc0 = (C0_MAX_BLOCKS + B - 1) / B;
+  nc0 = max(1, min(nc0, (T0 + C0_TT - 1) / C0_TT));
+  p.tchunk = ((T0 + nc0 - 1) / nc0 + C0_TT - 1) / C0_TT * C0_TT;
+  p.nc0 = (T0 + p.tchunk - 1) / p.tchunk;
+  return p;
+}
+int64_t slab_floats(int64_t S, int64_t n) { return S * n + (S > 32 ? (S + 31) / 32 * n : 0); }
+
+}  // namespace
+
+extern "C" int ste_w2v_conv0_ln_fwd(const float* wave, int64_t ldw, const float* w0, const float* bias,
+                                    const float* gamma, const float* beta, int B, int N, int T0, int C, int K0, int S0,
+                                    float eps, void* h, float* mean, float* rstd, void* stream) {
+  if (!c0_shape_ok(B, N, T0, C, K0, S0, ldw)) return STE_ERR_SHAPE;
+  const dim3 grid((T0 + C0_TT - 1) / C0_TT, B);
+  hipStream_t s = (hipStream_t)stream;
+#define STE_C0F(NCH, KT)                                                                                          \
+  hipLaunchKernelGGL((conv0_ln_fwd_kernel<NCH, KT>), grid, dim3(NT), 0, s, wave, ldw, w0, bias, gamma, beta, T0, C, \
+                     K0, S0, eps, mean, rstd, (bf16*)h)
+  if (C <= 256) {
+    if (K0 <= 10) STE_C0F(1, 10);
+    else STE_C0F(1, KMAX0);
+  } else {
+    if (K0 <= 10) STE_C0F(2, 10);
+    else STE_C0F(2, KMAX0);
+  }
+#undef STE_C0F
+  STE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t ste_w2v_conv0_ln_work(int B, int T0, int C, int K0) {
+  if (B <= 0 || T0 <= 0 || C <= 0 || (C & 3) || C > 512 || K0 <= 0 || K0 > KMAX0) return 0;
+  return slab_floats((int64_t)B * c0_plan(B, T0).nc0, (int64_t)C * (K0 + 3));
+}
+
+extern "C" int ste_w2v_conv0_ln_bwd(const float* dh, const float* wave, int64_t ldw, const float* mean,
+                                    const float* rstd, const float* w0, const float* bias, const float* gamma,
+                                    const float* beta, int B, int N, int T0, int C, int K0, int S0, float* dgamma,
+                                    float* dbeta, float* dbias, float* dw0, float* work, int64_t work_floats,
+                                    void* stream) {
+  if (!c0_shape_ok(B, N, T0, C, K0, S0, ldw) || !work || work_floats < ste_w2v_conv0_ln_work(B, T0, C, K0))
+    return STE_ERR_SHAPE;
+  const C0Plan p = c0_plan(B, T0);
+  const dim3 grid(p.nc0, B);
+  const int n = C * (K0 + 3);
+  const size_t lds = (size_t)n * sizeof(float);
+  hipStream_t s = (hipStream_t)stream;
+#define STE_C0B(NCH, KT)                                                                                           \
+  hipLaunchKernelGGL((conv0_ln_bwd_kernel<NCH, KT>), grid, dim3(NT), lds, s, dh, wave, ldw, mean, rstd, w0, bias,    \
+                     gamma, beta, T0, C, K0, S0, p.tchunk, work)
+  if (C <= 256) {
+    if (K0 <= 10) STE_C0B(1, 10);
+    else STE_C0B(1, KMAX0);
+  } else {
+    if (K0 <= 10) STE_C0B(2, 10);
+    else STE_C0B(2, KMAX0);
+  }
+#undef STE_C0B
+  STE_CHECK_LAUNCH();
+  ColSegs segs;
+  segs.out[0] = dw0; segs.end[0] = C * K0;
+  segs.out[1] = dgamma; segs.end[1] = C * (K0 + 1);
+  segs.out[2] = dbeta; segs.end[2] = C * (K0 + 2);
+  segs.out[3] = dbias; segs.end[3] = n;
+  return seg_sum(work, n, B * p.nc0, segs, s);
+}
+
+extern "C" int ste_w2v_ln_gelu_fwd(const void* z, const float* gamma, const float* beta, int64_t rows, int C,
+                                   float eps, void* h, int h_f32, float* mean, float* rstd, void* stream) {
+  if (!ln_shape_ok(rows, C)) return STE_ERR_SHAPE;
+  const dim3 grid(ln_blocks(rows));
+  hipStream_t s = (hipStream_t)stream;
+#define STE_LNF(NCH, VEC)                                                                                          \
+  do {                                                                                                             \
+    if (h_f32)                                                                                                     \
+      hipLaunchKernelGGL((ln_gelu_fwd_kernel<NCH, VEC, true>), grid, dim3(NT), 0, s, (const bf16*)z, gamma, beta,  \
+                         (int)rows, C, eps, mean, rstd, h);                                                        \
+    else                                                                                                           \
+      hipLaunchKernelGGL((ln_gelu_fwd_kernel<NCH, VEC, false>), grid, dim3(NT), 0, s, (const bf16*)z, gamma, beta, \
+                         (int)rows, C, eps, mean, rstd, h);                                                        \
+  } while (0)
+  if (ln_vec8(C, z, h)) {
+    if (C <= 512) STE_LNF(2, 8);
+    else STE_LNF(4, 8);
+  } else if (C <= 256) STE_LNF(1, 4);
+  else if (C <= 512) STE_LNF(2, 4);
+  else STE_LNF(4, 4);
+#undef STE_LNF
+  STE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int64_t ste_w2v_ln_gelu_work(int64_t rows, int C) {
+  if (!ln_shape_ok(rows, C)) return 0;
+  return slab_floats(ln_blocks(rows), (int64_t)3 * C);
+}
+
+extern "C" int ste_w2v_ln_gelu_bwd(const void* dh, int dh_bf16, const void* z, const float* mean, const float* rstd,
+                                   const float* gamma, const float* beta, int64_t rows, int C, void* dz, float* dgamma,
+                                   float* dbeta, float* dbias, float* work, int64_t work_floats, void* stream) {
+  if (!ln_shape_ok(rows, C)) return STE_ERR_SHAPE;
+  const bool sums = dgamma || dbeta || dbias;
+  if (sums && (!work || work_floats < ste_w2v_ln_gelu_work(rows, C))) return STE_ERR_SHAPE;
+  const int nblk = ln_blocks(rows);
+  const dim3 grid(nblk);
+  const size_t lds = sums ? (size_t)3 * C * sizeof(float) : 0;
+  float* part = sums ? work : nullptr;
+  hipStream_t s = (hipStream_t)stream;
+#define STE_LNB(NCH, VEC)                                                                                         \
+  do {                                                                                                            \
+    if (dh_bf16)                                                                                                  \
+      hipLaunchKernelGGL((ln_gelu_bwd_kernel<NCH, VEC, true>), grid, dim3(NT), lds, s, dh, (const bf16*)z, mean,  \
+                         rstd, gamma, beta, (int)rows, C, (bf16*)dz, part);                                       \
+    else                                                                                                          \
+      hipLaunchKernelGGL((ln_gelu_bwd_kernel<NCH, VEC, false>), grid, dim3(NT), lds, s, dh, (const bf16*)z, mean, \
+                         rstd, gamma, beta, (int)rows, C, (bf16*)dz, part);                                       \
+  } while (0)
+  if (ln_vec8(C, z, dz) && ln_vec8(C, dh, dh)) {
+    if (C <= 512) STE_LNB(2, 8);
+    else STE_LNB(4, 8);
+  } else if (C <= 256) STE_LNB(1, 4);
+  else if (C <= 512) STE_LNB(2, 4);
+  else STE_LNB(4, 4);
+#undef STE_LNB
+  STE_CHECK_LAUNCH();
+  if (!sums) return 0;
+  ColSegs segs;
+  segs.out[0] = dgamma; segs.end[0] = C;
+  segs.out[1] = dbeta; segs.end[1] = 2 * C;
+  segs.out[2] = dbias; segs.end[2] = 3 * C;
+  segs.out[3] = nullptr; segs.end[3] = 3 * C;
+  return seg_sum(work, (int64_t)3 * C, nblk, segs, s);
+}

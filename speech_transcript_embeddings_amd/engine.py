@@ -751,6 +751,98 @@ class Engine:
             self._db(dqkv, pre + nm["q"] + ".bias", fused=3)
         return dx0
 
+    def _preln_fwd(self, c, nm, i, x, nb, L, mask32, hp, ap, seed, save=True, act_p=0.0):
+        """One pre-LN transformer layer (Wav2Vec2EncoderLayerStableLayerNorm, tf:models/wav2vec2/
+        modeling_wav2vec2.py:611-654): x1 = x + drop(O(attn(QKV·LN1(x)))),
+        x2 = x1 + drop(W2·drop_act(gelu(W1·LN2(x1)))).  The residual stream x stays fp32; the
+        LayerNorms write the bf16 GEMM operands.  Same kernels, dropout-site seeds and saved-tensor
+        conventions as _postln_fwd."""
+        s = self.s
+        pre = nm["layer"].format(i=i)
+        M, D, F_ = x.shape[0], c.hidden_size, c.intermediate_size
+        H = c.num_attention_heads
+        eps = c.layer_norm_eps
+        tr = s.trainable_layer(pre + nm["q"] + ".weight")
+        sv = {"tr": tr, "seed": seed, "act_p": act_p}
+        a1 = self._e(M, D, dtype=BF16)
+        sv["st1"] = self._ln(x, pre + nm["ln1"], eps, yb=a1)
+        qkv = ops.linear(a1, s.fused(pre + nm["q"] + ".weight", 3, "w"), s.fused(pre + nm["q"] + ".bias", 3, "p"),
+                         out_bf16=True)
+        o = self._e(M, D, dtype=BF16)
+        o_lo = self._e(M, D, dtype=BF16) if save else None
+        lse = self._e(nb * H * L)
+        ops.attention_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], B=nb, T=L, H=H, o=o, lse=lse,
+                          key_mask=mask32, scale=1.0 / math.sqrt(D // H), drop_p=ap, seed=_site_seed(seed, 1),
+                          o_lo=o_lo, zero_masked_rows=True)
+        x1 = ops.linear(o, s.w(pre + nm["o"] + ".weight"), s.p(pre + nm["o"] + ".bias"),
+                        residual=x, drop_p=hp, seed=_site_seed(seed, 2))
+        a2 = self._e(M, D, dtype=BF16)
+        sv["st2"] = self._ln(x1, pre + nm["ln2"], eps, yb=a2)
+        zt = self._e(M, F_, dtype=BF16) if save else None  # GELU pre-activation, for backward only
+        h = ops.linear(a2, s.w(pre + nm["fi"] + ".weight"), s.p(pre + nm["fi"] + ".bias"),
+                       act=ACT_GELU, pre_out=zt, out_bf16=True, drop_p=act_p, seed=_site_seed(seed, 4))
+        x2 = ops.linear(h, s.w(pre + nm["fo"] + ".weight"), s.p(pre + nm["fo"] + ".bias"), residual=x1, drop_p=hp,
+                        seed=_site_seed(seed, 3))
+        sv.update(qkv=qkv, o=o, o_lo=o_lo, lse=lse, x=x, x1=x1, zt=zt)
+        if tr:
+            sv.update(a1=a1, a2=a2, h=h)
+        return x2, sv
+
+    def _preln_out_grad(self, c, nm, i, sv, hp):
+        """_ln_bwd keywords with which the LayerNorm backward ABOVE layer i (the next layer's LN1, or
+        the encoder's trailing LayerNorm) also emits what _preln_bwd(i) starts from: the bf16 copy of
+        the residual-stream gradient through the FFN output dropout, and its column sum, the
+        output_dense bias gradient."""
+        pre = nm["layer"].format(i=i)
+        M, D = sv["x"].shape
+        return dict(dxb=self._e(M, D, dtype=BF16), drop_p=hp, seed=_site_seed(sv["seed"], 3),
+                    dsum=self.s.g(pre + nm["fo"] + ".bias"))
+
+    def _preln_bwd(self, c, nm, i, sv, dx2, dx2b, nb, L, mask32, hp, ap, below=None):
+        """Backward of _preln_fwd.  dx2 fp32: gradient of the layer's output; dx2b: its bf16 copy
+        through the FFN output dropout (_preln_out_grad, written by the LayerNorm backward above).
+        below: the _preln_out_grad keywords of the next layer down that ran, so that this layer's
+        LN1 backward writes that layer's dx2b.  -> d input (fp32; below["dxb"] is filled)."""
+        s = self.s
+        pre = nm["layer"].format(i=i)
+        M, D = dx2.shape[0], c.hidden_size
+        H = c.num_attention_heads
+        tr = sv["tr"]
+        seed = sv["seed"]
+        dzt = self._dx(dx2b, pre + nm["fo"] + ".weight", act=ACT_GELU_BWD, z=sv["zt"], out_bf16=True,
+                       colsum=s.g(pre + nm["fi"] + ".bias"), drop_p=sv["act_p"], seed=_site_seed(seed, 4))
+        if tr:
+            self._dw(dx2b, sv["h"], pre + nm["fo"] + ".weight")
+        # dX GEMMs feeding an LN backward leave bf16 (as in _conformer_bwd); the stream stays fp32
+        da2 = self._dx(dzt, pre + nm["fi"] + ".weight", out_bf16=True)
+        if tr:
+            self._dw(dzt, sv["a2"], pre + nm["fi"] + ".weight")
+        del dzt
+        dx1 = self._e(M, D)
+        dx1b = self._e(M, D, dtype=BF16)
+        self._ln_bwd(da2, sv["x1"], sv["st2"], pre + nm["ln2"], dres=dx2, dx=dx1, dxb=dx1b, drop_p=hp,
+                     seed=_site_seed(seed, 2), dsum=s.g(pre + nm["o"] + ".bias"))
+        del da2
+        do = self._dx(dx1b, pre + nm["o"] + ".weight", out_bf16=True)
+        if tr:
+            self._dw(dx1b, sv["o"], pre + nm["o"] + ".weight")
+        del dx1b
+        qkv = sv["qkv"]
+        dqkv = self._e(M, 3 * D, dtype=BF16)
+        delta = self._e(nb * H * L)
+        ops.attention_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], sv["o"], sv["lse"], do, dqkv[:, :D],
+                          dqkv[:, D:2 * D], dqkv[:, 2 * D:], B=nb, T=L, H=H, delta=delta, key_mask=mask32,
+                          scale=1.0 / math.sqrt(D // H), drop_p=ap, seed=_site_seed(seed, 1), o_lo=sv["o_lo"])
+        del do, delta
+        da1 = self._dx(dqkv, pre + nm["q"] + ".weight", 3, out_bf16=True)
+        if tr:
+            self._dw(dqkv, sv["a1"], pre + nm["q"] + ".weight", fused=3)
+            self._db(dqkv, pre + nm["q"] + ".bias", fused=3)
+        del dqkv
+        dx0 = self._e(M, D)
+        self._ln_bwd(da1, sv["x"], sv["st1"], pre + nm["ln1"], dres=dx1, dx=dx0, **(below or {}))
+        return dx0
+
     def text_backward(self, dh, ctx, layers_done=None):
         """layers_done() is called once every trainable XLM-R layer's gradients are final (after
         the lowest trainable layer), so their all-reduce overlaps the frozen text layers' passes."""

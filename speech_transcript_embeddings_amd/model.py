@@ -37,6 +37,22 @@ _AUDIO_CONFIGS = {"facebook/w2v-bert-2.0": AudioConfig(),
                   "facebook/wav2vec2-base-100h": W2V2Config()}
 
 
+def _w2v2_large_ln():
+    """The large layer-norm wav2vec2 architecture (XLSR-53, XLS-R 300m, the -lv60 family): hidden
+    1024, 24 pre-LN layers, 16 heads, intermediate 4096, the 7 x 512 conv stack with bias and a
+    per-frame LayerNorm.  Only these architecture fields are set per name: dropout, layerdrop and
+    SpecAugment probabilities stay at transformers' Wav2Vec2Config defaults, because the package
+    downloads nothing and so never reads a checkpoint's config.json — pass a W2V2Config as
+    audio_model_name to override them.  audio_embedding_dim for these names is 1024."""
+    return W2V2Config(hidden_size=1024, num_hidden_layers=24, num_attention_heads=16, intermediate_size=4096,
+                      feat_extract_norm="layer", conv_bias=True, do_stable_layer_norm=True)
+
+
+_AUDIO_CONFIGS.update({n: _w2v2_large_ln() for n in (
+    "facebook/wav2vec2-large-xlsr-53", "facebook/wav2vec2-xls-r-300m", "facebook/wav2vec2-large-lv60",
+    "facebook/wav2vec2-large-960h-lv60", "facebook/wav2vec2-large-960h-lv60-self")})
+
+
 def _resolve(name_or_cfg, table, default_cls):
     if isinstance(name_or_cfg, (TextConfig, AudioConfig, W2V2Config)):
         return name_or_cfg
@@ -185,6 +201,11 @@ class EnhancedAudioTextModel(nn.Module):
             for n, p in params.items():
                 if n.endswith("parametrizations.weight.original0"):
                     p.copy_(params[n[:-1] + "1"].pow(2).sum(dim=(0, 1), keepdim=True).sqrt())
+                elif ".conv_layers." in n and n.endswith("conv.bias"):
+                    # conv_bias=True (layer-norm wav2vec2): transformers' U(-k, k), k = (Cin·kernel)^-1/2
+                    w = params[n[:-len("bias")] + "weight"]
+                    k = (w.shape[1] * w.shape[2]) ** -0.5
+                    p.uniform_(-k, k, generator=g)
 
     # ---------------------------------------------------------------- API
     @staticmethod

@@ -197,9 +197,15 @@ def _empty(*shape):
 # --------------------------------------------------------- audio (wav2vec2, raw waveform)
 @dataclass
 class W2V2Config:
-    """wav2vec2-base (transformers Wav2Vec2Config defaults, configuration_wav2vec2.py): the
-    raw-waveform encoder of SURVEY §8f rank 4.  Implemented: feat_extract_norm="group",
-    conv_bias=False, do_stable_layer_norm=False (post-LN layers), GELU, no adapter."""
+    """wav2vec2 (transformers Wav2Vec2Config defaults = wav2vec2-base, configuration_wav2vec2.py):
+    the raw-waveform encoder of SURVEY §8f rank 4.  GELU, no adapter.  Two architectures, the only
+    flag sets released checkpoints use:
+      feat_extract_norm="group", conv_bias=False, do_stable_layer_norm=False   wav2vec2-base:
+          GroupNorm after conv0 only, post-LN layers;
+      feat_extract_norm="layer", conv_bias=True, do_stable_layer_norm=True     XLSR-53, XLS-R, lv60:
+          conv bias + per-frame LayerNorm + GELU after every conv layer, pre-LN layers and a
+          trailing encoder LayerNorm (`layer_norm_arch`).
+    Any other mix raises NotImplementedError.  conv_dim entries may differ between layers."""
     hidden_size: int = 768
     num_hidden_layers: int = 12
     num_attention_heads: int = 12
@@ -223,11 +229,19 @@ class W2V2Config:
     do_stable_layer_norm: bool = False
 
     def __post_init__(self):
-        if self.feat_extract_norm != "group" or self.conv_bias or self.do_stable_layer_norm:
-            raise NotImplementedError("wav2vec2: only the base architecture (feat_extract_norm='group', "
-                                      "conv_bias=False, post-LN layers) is implemented")
+        flags = (self.feat_extract_norm, self.conv_bias, self.do_stable_layer_norm)
+        if flags not in (("group", False, False), ("layer", True, True)):
+            raise NotImplementedError("wav2vec2: implemented are the base architecture (feat_extract_norm='group', "
+                                      "conv_bias=False, post-LN layers) and the layer-norm one (feat_extract_norm="
+                                      "'layer', conv_bias=True, do_stable_layer_norm=True), not a mix: "
+                                      f"{flags}")
         self.conv_dim, self.conv_kernel, self.conv_stride = (tuple(self.conv_dim), tuple(self.conv_kernel),
                                                              tuple(self.conv_stride))
+
+    @property
+    def layer_norm_arch(self) -> bool:
+        """The XLSR / XLS-R / lv60 architecture (layer-norm feature encoder, pre-LN layers)."""
+        return self.feat_extract_norm == "layer"
 
     def frames(self, n_samples: int) -> list:
         """Sequence length after each conv layer: [N, T0, T1, ..., T_last]."""
@@ -238,19 +252,25 @@ class W2V2Config:
 
 
 class _W2VConv(nn.Module):
-    def __init__(self, cin, cout, k, s, group_norm):
+    """norm: "group" (Wav2Vec2GroupNormConvLayer, tf:…/modeling_wav2vec2.py:302-323), "layer"
+    (Wav2Vec2LayerNormConvLayer :275-299: nn.LayerNorm(cout), default eps 1e-5) or None (:254-272)."""
+
+    def __init__(self, cin, cout, k, s, norm, bias=False):
         super().__init__()
-        self.conv = nn.Conv1d(cin, cout, k, stride=s, bias=False)
-        if group_norm:
+        self.conv = nn.Conv1d(cin, cout, k, stride=s, bias=bias)
+        if norm == "group":
             self.layer_norm = nn.GroupNorm(cout, cout, affine=True)
+        elif norm == "layer":
+            self.layer_norm = nn.LayerNorm(cout, elementwise_affine=True)
 
 
 class _W2VFeatureEncoder(nn.Module):
     def __init__(self, c: W2V2Config):
         super().__init__()
         dims = (1,) + c.conv_dim
-        self.conv_layers = nn.ModuleList([_W2VConv(dims[i], dims[i + 1], c.conv_kernel[i], c.conv_stride[i], i == 0)
-                                          for i in range(len(c.conv_dim))])
+        norm = (lambda i: "layer") if c.layer_norm_arch else (lambda i: "group" if i == 0 else None)
+        self.conv_layers = nn.ModuleList([_W2VConv(dims[i], dims[i + 1], c.conv_kernel[i], c.conv_stride[i], norm(i),
+                                                   c.conv_bias) for i in range(len(c.conv_dim))])
 
 
 class _W2VFeatProj(nn.Module):
@@ -303,7 +323,8 @@ class _W2VFeedForward(nn.Module):
 
 
 class W2V2Layer(nn.Module):
-    """Wav2Vec2EncoderLayer (tf:models/wav2vec2/modeling_wav2vec2.py:575-608), post-LN."""
+    """Wav2Vec2EncoderLayer (tf:models/wav2vec2/modeling_wav2vec2.py:575-608), post-LN, and
+    Wav2Vec2EncoderLayerStableLayerNorm (:611-654), pre-LN: the same parameter tree."""
 
     def __init__(self, c: W2V2Config):
         super().__init__()

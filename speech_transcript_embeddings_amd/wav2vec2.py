@@ -24,6 +24,26 @@ the same strided views summed by ste_w2v_slab_sum; the positional conv's dX is t
 grouped GEMM with reversed taps (wf), its dW one batched GEMM whose k-major operands are the
 padded copies (row stride D/G again), then the weight-norm backward.
 
+The layer-norm architecture (W2V2Config.layer_norm_arch: feat_extract_norm="layer", conv_bias=True,
+do_stable_layer_norm=True — "facebook/wav2vec2-large-xlsr-53", "-xls-r-300m", the "-lv60" family)
+changes three stages of the schedule; everything else above is shared:
+
+  feature_extractor  :275-299  every conv layer is conv + bias + LayerNorm over the C channels of a
+                               frame + GELU.  conv0: ste_w2v_conv0_ln_fwd (one kernel, the pre-norm
+                               activation never reaches HBM); conv1..6: the same strided-view
+                               ste_gemm with the bias in its epilogue writing bf16 z, then
+                               ste_w2v_ln_gelu_fwd (bf16 out, fp32 out of the last layer)
+  encoder prologue   :729-769  x[~mask] = 0; x + GELU(pos_conv(x)); dropout — no LayerNorm here
+  layers             :611-654  pre-LN layers = Engine._preln_fwd on a fp32 residual stream, then
+                     :788      encoder.layer_norm LAST (the fp32 hidden state and its bf16 copy)
+
+and of the backward: ste_w2v_ln_gelu_bwd turns dh into the bf16 dz of the layer's dW / dX GEMMs
+(plus dγ, dβ and the conv-bias gradient), so ste_w2v_conv_fold runs without an activation
+derivative; ste_w2v_conv0_ln_bwd recomputes conv0 from the samples.  On the residual stream each
+LayerNorm backward (encoder.layer_norm, then every layer's LN1) also writes the bf16, dropped-out
+copy of the stream gradient and its column sum that the next layer down starts from
+(Engine._preln_out_grad), so no extra elementwise pass runs between layers.
+
 Masks: with an attention mask the frame mask follows the conv output lengths (padded frames
 zeroed before the positional conv and excluded as attention keys, as in transformers).  The
 reference itself cannot run that case (its pooling applies the SAMPLE-level mask to frame-level
@@ -42,6 +62,7 @@ from ._lib import ptr
 BF16, F32 = torch.bfloat16, torch.float32
 FE = "audio_encoder.feature_extractor.conv_layers."
 PC = "audio_encoder.encoder.pos_conv_embed.conv."
+CONV_LN_EPS = 1e-5   # the conv layers' nn.LayerNorm / nn.GroupNorm default eps (not layer_norm_eps)
 
 
 def _s():
@@ -79,23 +100,10 @@ def _conv_weight(e, l, cin, k):
     return out
 
 
-def forward(e, wave, mask_i64, train, base_seed, ctx, save=True, lengths=None):
-    """Raw waveform fp32 [B, N] (+ sample mask [B, N] or None) -> (hidden fp32 [B*T, D], bf16 copy).
-    lengths: host list of each clip's valid samples (SpecAugment's span sampling without a sync)."""
-    from .engine import W2V2_NAMES, _site_seed
+def _convs_fwd(e, wave, B, N, Ts, save):
+    """The base feature encoder -> (per-layer saves, conv output fp32, y0, gn_mean, gn_rstd)."""
     c = e.acfg
     s = e.s
-    if wave.dim() != 2:
-        raise ValueError(f"wav2vec2 input_values must be raw samples [B, N], got shape {tuple(wave.shape)}")
-    wave = wave.float().contiguous()
-    B, N = wave.shape
-    Ts = c.frames(N)
-    if min(Ts[1:]) <= 0:
-        raise ValueError(f"waveform of {N} samples is shorter than the conv stack's receptive field")
-    T = Ts[-1]
-    D = c.hidden_size
-    M = B * T
-    maskf, mask32 = frame_mask(c, mask_i64, B, N, T, wave.device)
     # ---- conv0 + GroupNorm + GELU
     C0, K0, S0 = c.conv_dim[0], c.conv_kernel[0], c.conv_stride[0]
     T0 = Ts[1]
@@ -124,6 +132,62 @@ def forward(e, wave, mask_i64, train, base_seed, ctx, save=True, lengths=None):
                  act=_lib.ACT_GELU, pre_out=z)
         convs.append(dict(z=z, wr=wr, h=None if last else out))
         h = out
+    return convs, h, y0, gn_mean, gn_rstd
+
+
+def _convs_ln_fwd(e, wave, B, N, Ts, save):
+    """The layer-norm feature encoder (same return form; no y0 / GroupNorm statistics): conv0 +
+    bias + LayerNorm + GELU in one kernel, then per layer the strided-view GEMM with the bias
+    epilogue writing bf16 z, and LayerNorm + GELU over z (fp32 out of the last layer)."""
+    c = e.acfg
+    s = e.s
+    C0, K0, S0 = c.conv_dim[0], c.conv_kernel[0], c.conv_stride[0]
+    T0 = Ts[1]
+    h = e._e(B * T0, C0, dtype=BF16)
+    mean, rstd = e._e(B * T0), e._e(B * T0)
+    _lib.call("ste_w2v_conv0_ln_fwd", ptr(wave), wave.stride(0), ptr(s.p(FE + "0.conv.weight")),
+              ptr(s.p(FE + "0.conv.bias")), ptr(s.p(FE + "0.layer_norm.weight")), ptr(s.p(FE + "0.layer_norm.bias")),
+              B, N, T0, C0, K0, S0, CONV_LN_EPS, ptr(h), ptr(mean), ptr(rstd), _s())
+    convs = [dict(h=h, mean=mean, rstd=rstd)]
+    nl = len(c.conv_dim)
+    for l in range(1, nl):
+        cin, cout, k, st = c.conv_dim[l - 1], c.conv_dim[l], c.conv_kernel[l], c.conv_stride[l]
+        Ti, To = Ts[l], Ts[l + 1]
+        wr = _conv_weight(e, l, cin, k)
+        a = torch.as_strided(h, (To, k * cin), (st * cin, 1))
+        z = e._e(B * To, cout, dtype=BF16)
+        ops.gemm(a, wr, M=To, N=cout, K=k * cin, batch=B, stride_a=Ti * cin, stride_c=To * cout, out=z,
+                 bias=s.p(FE + f"{l}.conv.bias"))
+        last = l == nl - 1
+        out = e._e(B * To, cout, dtype=F32 if last else BF16)
+        mean, rstd = e._e(B * To), e._e(B * To)
+        _lib.call("ste_w2v_ln_gelu_fwd", ptr(z), ptr(s.p(FE + f"{l}.layer_norm.weight")),
+                  ptr(s.p(FE + f"{l}.layer_norm.bias")), B * To, cout, CONV_LN_EPS, ptr(out), int(last), ptr(mean),
+                  ptr(rstd), _s())
+        convs.append(dict(z=z if save else None, wr=wr, h=None if last else out, mean=mean, rstd=rstd))
+        h = out
+    return convs, h, None, None, None
+
+
+def forward(e, wave, mask_i64, train, base_seed, ctx, save=True, lengths=None):
+    """Raw waveform fp32 [B, N] (+ sample mask [B, N] or None) -> (hidden fp32 [B*T, D], bf16 copy).
+    lengths: host list of each clip's valid samples (SpecAugment's span sampling without a sync)."""
+    from .engine import W2V2_NAMES, _site_seed
+    c = e.acfg
+    s = e.s
+    if wave.dim() != 2:
+        raise ValueError(f"wav2vec2 input_values must be raw samples [B, N], got shape {tuple(wave.shape)}")
+    wave = wave.float().contiguous()
+    B, N = wave.shape
+    Ts = c.frames(N)
+    if min(Ts[1:]) <= 0:
+        raise ValueError(f"waveform of {N} samples is shorter than the conv stack's receptive field")
+    T = Ts[-1]
+    D = c.hidden_size
+    M = B * T
+    maskf, mask32 = frame_mask(c, mask_i64, B, N, T, wave.device)
+    ln = c.layer_norm_arch
+    convs, h, y0, gn_mean, gn_rstd = (_convs_ln_fwd if ln else _convs_fwd)(e, wave, B, N, Ts, save)
     # ---- feature projection (+ dropout), SpecAugment, padded frames zeroed
     a0 = e._e(M, c.conv_dim[-1], dtype=BF16)
     st0 = e._ln(h, "audio_encoder.feature_projection.layer_norm", c.layer_norm_eps, yb=a0)
@@ -160,27 +224,43 @@ def forward(e, wave, mask_i64, train, base_seed, ctx, save=True, lengths=None):
     hp = c.hidden_dropout if train else 0.0
     ap = c.attention_dropout if train else 0.0
     act_p = c.activation_dropout if train else 0.0
-    x0 = e._e(M, D)
-    x0b = e._e(M, D, dtype=BF16)
     seed_ln = _site_seed(base_seed, 8)
-    st_enc = e._ln(xe, "audio_encoder.encoder.layer_norm", c.layer_norm_eps, y=x0, yb=x0b, drop_p=hp, seed=seed_ln)
+    if ln:   # pre-LN encoder (tf :729-802): dropout only here, the LayerNorm comes after the layers
+        if hp > 0:
+            _lib.call("ste_w2v_drop_rows", ptr(xe), M, D, float(hp), seed_ln & (2**64 - 1), None, _s())
+        x0, x0b, st_enc = xe, None, None
+    else:
+        x0 = e._e(M, D)
+        x0b = e._e(M, D, dtype=BF16)
+        st_enc = e._ln(xe, "audio_encoder.encoder.layer_norm", c.layer_norm_eps, y=x0, yb=x0b, drop_p=hp,
+                       seed=seed_ln)
     ctx.update(a_b=B, a_T=T, a_maskf=maskf, a_mask32=mask32, a_spec=spec,
                w2v=dict(wave=wave, N=N, Ts=Ts, y0=y0, gn_mean=gn_mean, gn_rstd=gn_rstd, convs=convs, a0=a0, st0=st0,
                         conv_out=h, p_fp=p_fp, seed_fp=seed_fp, norms=norms, wf=wf, xp=xp, cpad=cpad, xe=xe,
                         st_enc=st_enc, seed_ln=seed_ln, hp=hp, ap=ap, act_p=act_p))
     if not save:
         ctx["w2v"] = None
-    # ---- post-LN layers (layerdrop as transformers :700-712)
+    # ---- post-LN / pre-LN layers (layerdrop as transformers :700-712, :770-786)
     layers = []
     x, xb = x0, x0b
     for i in range(c.num_hidden_layers):
         if train and c.layerdrop > 0 and float(torch.rand([], generator=e.layerdrop_gen)) < c.layerdrop:
             layers.append(None)
             continue
-        x, xb, sv = e._postln_fwd(c, W2V2_NAMES, i, x, xb, B, T, mask32, hp, ap, _site_seed(base_seed, 100 + i),
-                                  save, act_p=act_p)
+        if ln:
+            x, sv = e._preln_fwd(c, W2V2_NAMES, i, x, B, T, mask32, hp, ap, _site_seed(base_seed, 100 + i), save,
+                                 act_p=act_p)
+        else:
+            x, xb, sv = e._postln_fwd(c, W2V2_NAMES, i, x, xb, B, T, mask32, hp, ap, _site_seed(base_seed, 100 + i),
+                                      save, act_p=act_p)
         layers.append(sv if save else None)
     ctx["a_layers"] = layers
+    if ln:   # the encoder's trailing LayerNorm (tf :788): the fp32 hidden state and its bf16 copy
+        xl = x
+        x, xb = e._e(M, D), e._e(M, D, dtype=BF16)
+        st_enc = e._ln(xl, "audio_encoder.encoder.layer_norm", c.layer_norm_eps, y=x, yb=xb)
+        if save:
+            ctx["w2v"].update(x_last=xl, st_enc=st_enc)
     return x, xb
 
 
@@ -206,10 +286,24 @@ def backward(e, dh, ctx, layers_done=None):
     M = B * T
     lo = next((i for i in range(c.num_hidden_layers)
                if s.trainable_layer(f"audio_encoder.encoder.layers.{i}.attention.q_proj.weight")), None)
+    ln = c.layer_norm_arch
     dx = dh
+    if ln:
+        # the trailing encoder LayerNorm; every LayerNorm backward on the residual stream also
+        # writes the bf16 / dropout / bias-sum form the next layer down starts from
+        ran = [i for i in range(c.num_hidden_layers) if ctx["a_layers"][i] is not None]
+        outg = {i: e._preln_out_grad(c, W2V2_NAMES, i, ctx["a_layers"][i], sv["hp"]) for i in ran}
+        below = dict(zip(ran[1:], ran[:-1]))   # layer -> the next one down that ran
+        dx = e._e(M, D)
+        e._ln_bwd(dh, sv["x_last"], sv["st_enc"], "audio_encoder.encoder.layer_norm", dx=dx,
+                  **(outg[ran[-1]] if ran else {}))
     for i in reversed(range(c.num_hidden_layers)):
         lsv = ctx["a_layers"][i]
-        if lsv is not None:
+        if lsv is not None and ln:
+            dx = e._preln_bwd(c, W2V2_NAMES, i, lsv, dx, outg.pop(i)["dxb"], B, T, mask32, sv["hp"], sv["ap"],
+                              below=outg.get(below.get(i)))
+            ctx["a_layers"][i] = None
+        elif lsv is not None:
             dx = e._postln_bwd(c, W2V2_NAMES, i, lsv, dx, B, T, mask32, sv["hp"], sv["ap"])
             ctx["a_layers"][i] = None
         if layers_done is not None and i == lo:
@@ -218,10 +312,17 @@ def backward(e, dh, ctx, layers_done=None):
         layers_done()
     if not _needs_grad_below_layers(s):
         return
-    # ---- encoder LayerNorm (its output dropout undone on dy)
-    dxe = e._e(M, D)
-    e._ln_bwd(dx, sv["xe"], sv["st_enc"], "audio_encoder.encoder.layer_norm", dx=dxe, in_drop_p=sv["hp"],
-              in_seed=sv["seed_ln"])
+    if ln:
+        # ---- the prologue's dropout, in place on the gradient
+        dxe = dx
+        if sv["hp"] > 0:
+            _lib.call("ste_w2v_drop_rows", ptr(dxe), M, D, float(sv["hp"]), int(sv["seed_ln"]) & (2**64 - 1), None,
+                      _s())
+    else:
+        # ---- encoder LayerNorm (its output dropout undone on dy)
+        dxe = e._e(M, D)
+        e._ln_bwd(dx, sv["xe"], sv["st_enc"], "audio_encoder.encoder.layer_norm", dx=dxe, in_drop_p=sv["hp"],
+                  in_seed=sv["seed_ln"])
     # ---- positional conv: xe = x + gelu(conv(x) + bias)
     G, Kp = c.num_conv_pos_embedding_groups, c.num_conv_pos_embeddings
     Cg = D // G
@@ -275,16 +376,23 @@ def backward(e, dh, ctx, layers_done=None):
     e._ln_bwd(da0, sv["conv_out"], sv["st0"], "audio_encoder.feature_projection.layer_norm", dx=dcur)
     del da0
     # ---- conv stack, top down: dz_l = dh_l · gelu'(z_l) (bf16), dW_l, dcol -> fold -> dh_{l-1}
+    # (layer-norm architecture: dz_l = LN'(dh_l · gelu') from ste_w2v_ln_gelu_bwd, and the fold
+    # applies no activation derivative)
     convs = sv["convs"]
     cl = c.conv_dim[-1]
-    dz = e._e(B * Ts[nl], cl, dtype=BF16)
-    _lib.call("ste_w2v_conv_fold", ptr(dcur), cl, ptr(convs[nl - 1]["z"]), B, Ts[nl], Ts[nl], cl, 1, 1, ptr(dz), 1,
-              _s())
+    if ln:
+        dz = dcur
+    else:
+        dz = e._e(B * Ts[nl], cl, dtype=BF16)
+        _lib.call("ste_w2v_conv_fold", ptr(dcur), cl, ptr(convs[nl - 1]["z"]), B, Ts[nl], Ts[nl], cl, 1, 1, ptr(dz),
+                  1, _s())
     del dcur
     for l in range(nl - 1, 0, -1):
         cin, cout, k, st = c.conv_dim[l - 1], c.conv_dim[l], c.conv_kernel[l], c.conv_stride[l]
         Ti, To = Ts[l], Ts[l + 1]
         hin = convs[l - 1]["h"]
+        if ln:
+            dz = _ln_gelu_bwd(e, l, dz, convs[l], B * To, cout)
         gw = s.g(FE + f"{l}.conv.weight")
         if gw is not None:
             # per-clip dW slabs [B][Co][k·Ci] (the strided views of different clips are not one
@@ -303,11 +411,13 @@ def backward(e, dh, ctx, layers_done=None):
         dcol = ops.linear_dx(dz, convs[l]["wr"])          # [B*To, k·Ci] fp32
         first = l == 1
         dprev = e._e(B * Ti, cin, dtype=F32 if first else BF16)
-        _lib.call("ste_w2v_conv_fold", ptr(dcol), k * cin, None if first else ptr(convs[l - 1]["z"]), B, Ti, To, cin,
-                  k, st, ptr(dprev), 0 if first else 1, _s())
+        _lib.call("ste_w2v_conv_fold", ptr(dcol), k * cin, None if first or ln else ptr(convs[l - 1]["z"]), B, Ti, To,
+                  cin, k, st, ptr(dprev), 0 if first else 1, _s())
         del dcol
         dz = dprev
     else:
+        if ln:
+            return _conv0_ln_bwd(e, dz, sv, B)
         # ---- conv0 + GroupNorm + GELU (dz is dL/dh0 in fp32 here)
         C0, K0, S0 = c.conv_dim[0], c.conv_kernel[0], c.conv_stride[0]
         T0 = Ts[1]
@@ -319,12 +429,50 @@ def backward(e, dh, ctx, layers_done=None):
                   ptr(s.g(FE + "0.layer_norm.bias")), ptr(s.g(FE + "0.conv.weight")), ptr(work), nwork, _s())
 
 
+def _ln_gelu_bwd(e, l, dh, cv, rows, cout):
+    """Conv layer l >= 1 of the layer-norm architecture: dh (fp32 or bf16) -> dz bf16, and the
+    gradients of the layer's LayerNorm affine and conv bias."""
+    s = e.s
+    dz = e._e(rows, cout, dtype=BF16)
+    gg, gb, gcb = s.g(FE + f"{l}.layer_norm.weight"), s.g(FE + f"{l}.layer_norm.bias"), s.g(FE + f"{l}.conv.bias")
+    nwork = 0 if gg is None and gb is None and gcb is None else int(_lib.fn("ste_w2v_ln_gelu_work")(rows, cout))
+    work = e._e(nwork) if nwork else None
+    _lib.call("ste_w2v_ln_gelu_bwd", ptr(dh), int(dh.dtype == BF16), ptr(cv["z"]), ptr(cv["mean"]), ptr(cv["rstd"]),
+              ptr(s.p(FE + f"{l}.layer_norm.weight")), ptr(s.p(FE + f"{l}.layer_norm.bias")), rows, cout, ptr(dz),
+              ptr(gg), ptr(gb), ptr(gcb), ptr(work), nwork, _s())
+    return dz
+
+
+def _conv0_ln_bwd(e, dh0, sv, B):
+    """conv0 + bias + LayerNorm + GELU of the layer-norm architecture (dh0 = dL/dh0, fp32)."""
+    c = e.acfg
+    s = e.s
+    C0, K0, S0 = c.conv_dim[0], c.conv_kernel[0], c.conv_stride[0]
+    T0 = sv["Ts"][1]
+    cv = sv["convs"][0]
+    nwork = int(_lib.fn("ste_w2v_conv0_ln_work")(B, T0, C0, K0))
+    work = e._e(nwork)
+    _lib.call("ste_w2v_conv0_ln_bwd", ptr(dh0), ptr(sv["wave"]), sv["wave"].stride(0), ptr(cv["mean"]),
+              ptr(cv["rstd"]), ptr(s.p(FE + "0.conv.weight")), ptr(s.p(FE + "0.conv.bias")),
+              ptr(s.p(FE + "0.layer_norm.weight")), ptr(s.p(FE + "0.layer_norm.bias")), B, sv["N"], T0, C0, K0, S0,
+              ptr(s.g(FE + "0.layer_norm.weight")), ptr(s.g(FE + "0.layer_norm.bias")), ptr(s.g(FE + "0.conv.bias")),
+              ptr(s.g(FE + "0.conv.weight")), ptr(work), nwork, _s())
+
+
+def _has_grad(s, name):
+    return name in s.slots and s.g(name) is not None
+
+
 def _needs_grad_conv0(s):
-    return any(s.g(FE + n) is not None for n in ("0.conv.weight", "0.layer_norm.weight", "0.layer_norm.bias"))
+    return any(_has_grad(s, FE + n) for n in ("0.conv.weight", "0.conv.bias", "0.layer_norm.weight",
+                                              "0.layer_norm.bias"))
 
 
 def _needs_grad_conv(s, c):
-    return any(s.g(FE + f"{l}.conv.weight") is not None for l in range(len(c.conv_dim))) or _needs_grad_conv0(s)
+    """Any conv-stack parameter (layers >= 1 carry a bias and LayerNorm affines only in the
+    layer-norm architecture)."""
+    return any(_has_grad(s, FE + f"{l}.{n}") for l in range(1, len(c.conv_dim))
+               for n in ("conv.weight", "conv.bias", "layer_norm.weight", "layer_norm.bias")) or _needs_grad_conv0(s)
 
 
 def _needs_grad_below_layers(s):
