@@ -258,10 +258,19 @@ __global__ __launch_bounds__(NT) void mean_pool_fwd_kernel(const T* h, const int
   const float inv = cls ? 1.f : 1.f / fmaxf(cnt, 1e-9f);
   for (int l = tid; l < L; l += NT) weights[b * L + l] = sc[l] * inv;
   const int Lr = cls ? 1 : L;  // CLS reads one row
+  // two-level sum (MEAN_BLK rows into a block sum, block sums into the total): one running fp32 sum
+  // over L = 16384 rows of a common sign rounds every add at the magnitude of the whole sum and
+  // ends 25x further from fp64 than a pairwise fp32 sum; L <= MEAN_BLK is the plain serial sum
+  constexpr int MEAN_BLK = 128;
   for (int c = tid * 4; c < H; c += NT * 4) {
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int l = 0; l < Lr; ++l)
-      if (sc[l] != 0.f) acc += ld4(h + (int64_t)(b * L + l) * H + c);
+    for (int l0 = 0; l0 < Lr; l0 += MEAN_BLK) {
+      f32x4 blk = {0.f, 0.f, 0.f, 0.f};
+      const int l1 = min(Lr, l0 + MEAN_BLK);
+      for (int l = l0; l < l1; ++l)
+        if (sc[l] != 0.f) blk += ld4(h + (int64_t)(b * L + l) * H + c);
+      acc += blk;
+    }
     acc *= inv;
     *reinterpret_cast<f32x4*>(pooled + (int64_t)b * H + c) = acc;
     if (pooled_bf16) store_bf16x4(pooled_bf16 + (int64_t)b * H + c, acc);

@@ -1634,23 +1634,30 @@ def test_adamw_clip(ops):
 def test_adamw_split_invariant(ops):
     """The update of an element does not depend on how the flat buffer is cut into launches (bulk
     two-group loop, one-group loop, scalar tail all round alike): TrainStep(overlap_optimizer=True)
-    runs AdamW per parameter block and must match the one-launch-per-group update bit for bit."""
-    torch.manual_seed(9)
-    n = 3_000_011
-    p0 = torch.randn(n, device=DEV)
-    g = torch.randn(n, device=DEV) * 0.01
-    m0 = torch.randn(n, device=DEV) * 1e-3
-    v0 = torch.rand(n, device=DEV) * 1e-5
-    acc = torch.zeros(1, device=DEV, dtype=torch.float64)
-    ops.sumsq(g, acc)
-    kw = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01, step=3, sumsq_acc=acc, max_norm=1.0)
-    outs = []
-    for cuts in ([0, n], [0, 4, 1_048_580, 1_048_600, 2_999_996, n], [0, 123_456, 2_000_000, n]):
-        p, m, v = p0.clone(), m0.clone(), v0.clone()
-        pb = torch.empty(n, device=DEV, dtype=torch.bfloat16)
-        for a, b in zip(cuts, cuts[1:]):
-            ops.adamw(p[a:b], g[a:b], m[a:b], v[a:b], pb[a:b], **kw)
-        outs.append((p, m, v, pb))
-    for o in outs[1:]:
-        for x, y in zip(outs[0], o):
-            assert torch.equal(x, y)
+    runs AdamW per parameter block and must match the one-launch-per-group update bit for bit.
+    The grid is capped at 8192 blocks of 1024 elements, so the bulk loop (i + stride + 3 < n) needs
+    n > 8,388,608 + 3: n = 3,000,011 compares the one-group loop and the scalar tail under different
+    cuts and never ran the bulk loop; n = 20,971,527 (2.5 strides + 7) runs it for every thread in
+    the single launch, against launches of at most 4,000,000 elements, which never enter it."""
+    n_bulk = 20_971_527
+    for n, cutsets in ((3_000_011, ([0, 4, 1_048_580, 1_048_600, 2_999_996, 3_000_011], [0, 123_456, 2_000_000, 3_000_011])),
+                       (n_bulk, (list(range(0, n_bulk, 4_000_000)) + [n_bulk],))):
+        torch.manual_seed(9)
+        p0 = torch.randn(n, device=DEV)
+        g = torch.randn(n, device=DEV) * 0.01
+        m0 = torch.randn(n, device=DEV) * 1e-3
+        v0 = torch.rand(n, device=DEV) * 1e-5
+        acc = torch.zeros(1, device=DEV, dtype=torch.float64)
+        ops.sumsq(g, acc)
+        kw = dict(lr=1e-3, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01, step=3, sumsq_acc=acc, max_norm=1.0)
+        outs = []
+        for cuts in ([0, n],) + tuple(cutsets):
+            assert all(c % 4 == 0 for c in cuts[:-1])
+            p, m, v = p0.clone(), m0.clone(), v0.clone()
+            pb = torch.empty(n, device=DEV, dtype=torch.bfloat16)
+            for a, b in zip(cuts, cuts[1:]):
+                ops.adamw(p[a:b], g[a:b], m[a:b], v[a:b], pb[a:b], **kw)
+            outs.append((p, m, v, pb))
+        for o in outs[1:]:
+            for x, y in zip(outs[0], o):
+                assert torch.equal(x, y)
