@@ -312,6 +312,38 @@ int64_t ste_glu_dwconv_bwd_ws_floats(int B, int T, int C, int K);
 int ste_fbank(const float* wav, int64_t ld_wav, const int32_t* lengths, int B, int Tmax, float pad_value,
               float* feats, int64_t* mask, int mask_mode, float* work, void* stream);
 
+/* --------------------------------------------------------------- resample --
+ * Native-rate clips -> the 16 kHz every audio entry point above and below expects: replaces the
+ * CPU resampling of the reference's data workers (ref:training/trainer_unfreeze.py:1927
+ * `Audio(sampling_rate=16000)`, ref:processor.py:82-85 `librosa.resample`).  Those go through soxr /
+ * FFmpeg, whose filters have no closed form, so the filter is this library's own: a rational
+ * polyphase Kaiser-windowed sinc.  g = gcd(sr_in, sr_out), M = sr_in/g, L = sr_out/g,
+ * c = rolloff·min(L, M), hw = ceil(Z·M/c), K = 2·hw taps (Z = 64, rolloff = 0.9475937167399596,
+ * beta = 14.769656459379492).  A clip of n_in samples gives n_out = ceil(n_in·L/M) outputs;
+ * output n reads source samples m = floor(n·M/L) - hw + 1 .. floor(n·M/L) + hw (zero outside
+ * [0, n_in)) with h = (c/M)·sinc(t)·I0(beta·sqrt(1 - (t/Z)²))/I0(beta), t = (m·L - n·M)·c/(M·L),
+ * for |t| < Z, else 0.
+ * ste_resample_plan (host only): M, L, K of a rate pair (each pointer may be NULL).  STE_ERR_ARG for a
+ *   non-positive rate; STE_ERR_SHAPE beyond the caps L <= 1024 phases, K <= 2048 taps (a thread's
+ *   phase is its index modulo L within a workgroup of at most 1024 threads; the K-tap window and the
+ *   tile's samples share 64 KB of LDS).
+ * ste_resample_table (host only): the L·K coefficients, double-precision arithmetic rounded once to
+ *   fp32, tap-major table[t·L + i] (tap t of phase i = n mod L), into a HOST buffer of
+ *   table_floats >= L·K floats.
+ * ste_resample: wav fp32 [B, ld_wav], lengths int32 [B], table (a device copy of the above); writes
+ *   out[b, n] for n < n_out_max (<= ld_out): the filtered value for n < n_out(b), exactly 0.0f past
+ *   it, and out_lengths[b] = n_out(b) (may be NULL).  wav beyond lengths[b] is never read as data.
+ *   One thread sums each output's taps in fp32 in an order fixed by (M, L, K): the result for a clip
+ *   does not depend on the batch, the row strides or the tile.  STE_ERR_SHAPE also when no tile of
+ *   this (M, L, K) fits the LDS (L > 256 with M beyond ~14,000) or B > 65535.
+ * ste_resample_tile (host only): consecutive outputs per workgroup for (M, L, K) (1024 on the
+ *   integer-decimation kernel, L = 1 and M = 2 or 3; else a multiple of L); 0 for a bad shape. */
+int ste_resample_plan(int sr_in, int sr_out, int* M, int* L, int* K);
+int ste_resample_table(int sr_in, int sr_out, float* table, int64_t table_floats);
+int ste_resample_tile(int M, int L, int K);
+int ste_resample(const float* wav, int64_t ld_wav, const int32_t* lengths, int B, int M, int L, int K,
+                 const float* table, float* out, int64_t ld_out, int n_out_max, int32_t* out_lengths, void* stream);
+
 /* ------------------------------------------------------------------ heads --
  * AttentivePooling (ref:training/trainer_unfreeze.py:171-211) after its first
  * Linear+tanh has run through ste_gemm: score = t·w2 + b2, masked softmax over

@@ -145,6 +145,11 @@ _SIGS = {
     "ste_glu_dwconv_bwd_ws_floats": (c_int64, [c_int, c_int, c_int, c_int]),
     "ste_fbank": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_void_p,
                           c_void_p]),
+    "ste_resample_plan": (c_int, [c_int, c_int, C.POINTER(c_int), C.POINTER(c_int), C.POINTER(c_int)]),
+    "ste_resample_table": (c_int, [c_int, c_int, c_void_p, c_int64]),
+    "ste_resample_tile": (c_int, [c_int, c_int, c_int]),
+    "ste_resample": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
+                             c_int, c_void_p, c_void_p]),
     "ste_gemm_mx8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "ste_gemm_mx8_kernel": (c_int, [C.POINTER(GemmArgs), c_int]),
     "ste_gemm_plan_min_tiles": (c_int, [c_int, c_int, C.POINTER(c_int), C.POINTER(c_int)]),

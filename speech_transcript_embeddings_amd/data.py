@@ -39,6 +39,7 @@ REPLACE_WORDS = ("sim", "não", "e", "o", "de", "um", "uma", "tua", "qualquer", 
                  "imaginemos")
 INSERT_WORDS = ("sim", "não", "e", "o", "de", "um", "uma")
 STRATEGIES = ("replace", "shuffle", "drop", "add", "partial")
+TARGET_RATE = 16000   # what every audio entry point expects; other rates are resampled on the GPU
 
 
 def create_corrupted_transcript(text: str, rng=random) -> str:
@@ -111,6 +112,10 @@ class CommonVoiceDataset(torch.utils.data.Dataset):
         out = {"input_ids_pos": ids_p, "attention_mask_pos": m_p, "input_ids_neg": ids_n, "attention_mask_neg": m_n}
         if self.raw_audio:
             out["waveform"] = torch.as_tensor(np.asarray(speech, dtype=np.float32)).reshape(-1)
+            # a clip at its native rate (Common Voice: 48 kHz) is resampled on the GPU by to_model_batch
+            sr = item["audio"].get("sampling_rate") if hasattr(item["audio"], "get") else None
+            if sr is not None and int(sr) != self.sampling_rate:
+                out["sampling_rate"] = int(sr)
             return out
         feats = self.feature_extractor(speech, sampling_rate=self.sampling_rate, return_tensors="pt")
         x = feats["input_features"] if "input_features" in feats else feats["input_values"]
@@ -138,25 +143,59 @@ def waveform_collate_fn(batch):
     out["waveform"] = wav
     out["lengths"] = lens
     out["is_corrupted"] = torch.zeros(len(waves), dtype=torch.long)
+    # host list of the clips' native rates, only when some item carries one (the dataset adds
+    # "sampling_rate" to items that differ from its target rate)
+    if any("sampling_rate" in b for b in batch):
+        out["sampling_rates"] = [int(b.get("sampling_rate", TARGET_RATE)) for b in batch]
     return out
+
+
+def resample_batch(wav, lens, host_lens, rates, sr_out=TARGET_RATE):
+    """wav [B, N] / lens int32 [B] on the GPU with per-clip native rates (host list) -> (wav at
+    sr_out [B, N'], lens [B], host lengths): one ops.resample launch per distinct rate over the
+    rows of that rate, written back to their rows of one zero-padded batch.  The row selections
+    are built from host lists, so nothing is read back from the device."""
+    from . import ops
+    new_host = [ops.resampled_length(n, r, sr_out) for n, r in zip(host_lens, rates)]
+    distinct = sorted(set(rates))
+    if distinct == [sr_out]:
+        return wav, lens, new_host
+    if len(distinct) == 1:
+        w, l = ops.resample(wav, lens, distinct[0], sr_out)
+        return w, l, new_host
+    B, N = wav.shape
+    width = max(ops.resampled_length(N, r, sr_out) for r in distinct)
+    out = torch.zeros(B, width, device=wav.device, dtype=torch.float32)
+    out_lens = torch.empty(B, device=wav.device, dtype=torch.int32)
+    for r in distinct:
+        rows = torch.tensor([i for i, x in enumerate(rates) if x == r], device=wav.device)
+        w, l = ops.resample(wav.index_select(0, rows), lens.index_select(0, rows).contiguous(), r, sr_out)
+        out[rows, : w.shape[1]] = w
+        out_lens[rows] = l
+    return out, out_lens, new_host
 
 
 def to_model_batch(batch, device="cuda", pad_value=1.0, non_blocking=True):
     """A waveform_collate_fn batch -> the reference's model batch on `device`: the text
     tensors moved, input_values [B, T, 160] / attention_mask_audio [B, T] from the batched
     fbank kernel with custom_collate_fn's semantics (per-clip features, zero rows and mask 0
-    past each clip's frames)."""
+    past each clip's frames).  A batch with "sampling_rates" is resampled to 16 kHz on the GPU
+    first (ops.resample), where the reference's workers resample on the CPU (ref:1927)."""
     from . import ops
     dev = torch.device(device)
-    out = {k: v.to(dev, non_blocking=non_blocking) for k, v in batch.items() if k not in ("waveform", "lengths")}
+    skip = ("waveform", "lengths", "sampling_rates")
+    out = {k: v.to(dev, non_blocking=non_blocking) for k, v in batch.items() if k not in skip}
     wav = batch["waveform"].to(dev, non_blocking=non_blocking)
     lens = batch["lengths"].to(dev, non_blocking=non_blocking)
-    T = max(1, max(num_frames(int(n)) for n in batch["lengths"].tolist()))
+    host = [int(n) for n in batch["lengths"].tolist()]
+    if "sampling_rates" in batch:
+        wav, lens, host = resample_batch(wav, lens, host, batch["sampling_rates"])
+    T = max(1, max(num_frames(n) for n in host))
     feats, mask = ops.fbank(wav, lens, T, pad_value=pad_value, mask_mode=0)
     out["input_values"] = feats
     out["attention_mask_audio"] = mask
     # host-known frame counts: SpecAugment's span sampling reads these instead of the device mask
-    out["audio_lengths"] = [num_frames(int(n)) for n in batch["lengths"].tolist()]
+    out["audio_lengths"] = [num_frames(n) for n in host]
     return out
 
 

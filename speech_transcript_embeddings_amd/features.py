@@ -76,10 +76,13 @@ class SeamlessM4TFeatureExtractor:
             raise ValueError("empty waveform")
         lens = [c.numel() for c in clips]
         N = max(lens)
-        wav = torch.zeros(len(clips), N, dtype=torch.float32)
-        for i, c in enumerate(clips):
-            wav[i, : lens[i]] = c
-        wav = wav.to(self.device, non_blocking=True)
+        if len(clips) == 1 and clips[0].device == self.device:
+            wav = clips[0].reshape(1, N).contiguous()   # already on the GPU (process_audio_array): no host trip
+        else:
+            wav = torch.zeros(len(clips), N, dtype=torch.float32)
+            for i, c in enumerate(clips):
+                wav[i, : lens[i]] = c
+            wav = wav.to(self.device, non_blocking=True)
         lengths = torch.tensor(lens, dtype=torch.int32, device=self.device)
         T = max(num_frames(n) for n in lens)
         feats, mask = ops.fbank(wav, lengths, max(T, 1), pad_value=self.padding_value, mask_mode=1)
@@ -87,6 +90,27 @@ class SeamlessM4TFeatureExtractor:
         if return_attention_mask:
             out["attention_mask"] = mask
         return out
+
+
+def process_audio_array(audio_array, orig_sr, *, extractor, max_audio_length=480000):
+    """The audio half of the reference's AudioTextProcessor.process_audio_array (ref:processor.py:79-126),
+    in its order: resample to the extractor's rate (ops.resample on the GPU where the reference calls
+    librosa.resample), divide by max|x| when that exceeds 1, trim to max_audio_length samples, extract.
+    Returns {"input_features" [1, T, 160], "attention_mask_audio" [1, T]} on the extractor's device."""
+    dev = extractor.device
+    x = torch.as_tensor(np.asarray(audio_array, dtype=np.float32) if not torch.is_tensor(audio_array)
+                        else audio_array, dtype=torch.float32).reshape(1, -1).to(dev)
+    if x.shape[1] == 0:
+        raise ValueError("empty waveform")
+    n = x.shape[1]
+    if int(orig_sr) != extractor.sampling_rate:
+        lengths = torch.full((1,), n, dtype=torch.int32, device=dev)
+        x, _ = ops.resample(x.contiguous(), lengths, int(orig_sr), extractor.sampling_rate)
+    # x / max|x| where max|x| > 1 (ref:91-92), as one device expression: dividing by 1.0 changes nothing
+    x = x / x.abs().max().clamp(min=1.0)
+    x = x[:, :max_audio_length]
+    feats = extractor(x.reshape(-1), sampling_rate=extractor.sampling_rate, return_tensors="pt")
+    return {"input_features": feats["input_features"], "attention_mask_audio": feats.get("attention_mask")}
 
 
 def custom_collate_fn(batch):

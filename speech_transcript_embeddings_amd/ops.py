@@ -522,6 +522,67 @@ def fbank(wav, lengths, Tmax, *, pad_value=1.0, mask_mode=0, feats=None, mask=No
     return feats, mask
 
 
+# --------------------------------------------------------------- resample
+def resample_plan(sr_in, sr_out=16000):
+    """(M, L, K) of a rate pair (host only): M/L the reduced ratio, K taps per output."""
+    M, L, K = C.c_int(), C.c_int(), C.c_int()
+    call("ste_resample_plan", int(sr_in), int(sr_out), C.byref(M), C.byref(L), C.byref(K))
+    return M.value, L.value, K.value
+
+
+def resampled_length(n, sr_in, sr_out=16000):
+    """Samples a clip of n samples at sr_in has at sr_out: ceil(n·L/M) (host arithmetic)."""
+    if sr_in == sr_out:
+        return int(n)
+    M, L, _ = resample_plan(sr_in, sr_out)
+    return (int(n) * L + M - 1) // M
+
+
+def resample_tile(sr_in, sr_out=16000):
+    """Consecutive outputs one workgroup of ste_resample produces for this rate pair."""
+    return fn("ste_resample_tile")(*resample_plan(sr_in, sr_out))
+
+
+# device copies of the coefficient tables, keyed (sr_in, sr_out, device): constants of a rate pair
+# (not weights, so not ParamStore's protocol), built once on the host by ste_resample_table
+_RESAMPLE_TABLES = {}
+
+
+def _resample_table(sr_in, sr_out, dev):
+    key = (int(sr_in), int(sr_out), dev)
+    t = _RESAMPLE_TABLES.get(key)
+    if t is None:
+        _, L, K = resample_plan(sr_in, sr_out)
+        host = torch.empty(L * K, dtype=F32)
+        call("ste_resample_table", int(sr_in), int(sr_out), host.data_ptr(), host.numel())
+        t = _RESAMPLE_TABLES[key] = host.to(dev)
+    return t
+
+
+def resample(wav, lengths, sr_in, sr_out=16000, *, out=None):
+    """wav fp32 [B, N] (rows padded; the padding is never read), lengths int32 [B] on the GPU ->
+    (out fp32 [B, ceil(N·L/M)] with zeros past each clip, out_lengths int32 [B]).  sr_in == sr_out
+    returns the inputs unchanged with no launch.  `out`: a row-major [B, n_out_max] destination."""
+    if int(sr_in) == int(sr_out):
+        return wav, lengths
+    M, L, K = resample_plan(sr_in, sr_out)
+    B, N = wav.shape
+    dev = wav.device
+    if not wav.is_cuda or lengths.device != dev or lengths.shape != (B,):
+        raise ValueError("resample expects wav [B, N] and lengths [B] on the same GPU")
+    assert wav.dtype == F32 and wav.stride(1) == 1 and lengths.dtype == torch.int32 and lengths.is_contiguous()
+    if out is None:
+        out = torch.empty((B, (N * L + M - 1) // M), device=dev, dtype=F32)
+    assert out.device == dev and out.dtype == F32 and out.shape[0] == B and (out.shape[1] <= 1 or out.stride(1) == 1)
+    if B == 0 or N == 0 or out.shape[1] == 0:
+        return out.zero_(), torch.zeros(B, device=dev, dtype=torch.int32)
+    out_lengths = torch.empty(B, device=dev, dtype=torch.int32)
+    table = _resample_table(sr_in, sr_out, dev)
+    call("ste_resample", ptr(wav), wav.stride(0), ptr(lengths), B, M, L, K, ptr(table), ptr(out),
+         out.stride(0), out.shape[1], ptr(out_lengths), _s())
+    return out, out_lengths
+
+
 # ------------------------------------------------------------------ heads
 def attn_pool_fwd(t, w2, b2, h, mask, B, L, weights, pooled, pooled_bf16=None):
     call("ste_attn_pool_fwd", ptr(t), ptr(w2), ptr(b2), ptr(h), ptr(mask), B, L, t.shape[-1], h.shape[-1],

@@ -10,6 +10,8 @@ through them); the fused training step itself calls the C ABI directly (engine.p
 
     ste::fbank(wav, lengths, t_max, pad_value, mask_mode) -> (features, mask)
         SeamlessM4TFeatureExtractor + custom_collate_fn (ref :856-866, :880-921)
+    ste::resample(wav, lengths, sr_in, sr_out) -> (wav_out, lengths_out)
+        Audio(sampling_rate=16000) / librosa.resample of the data workers (ref :1927, processor.py:82-85)
     ste::linear(x, weight, bias?) -> y                       nn.Linear, bf16 MFMA / fp32 accumulate
     ste::layer_norm(x, weight, bias, eps) -> (y, mean, rstd) nn.LayerNorm
     ste::attention(q, k, v, key_mask?, rel_E?, scale, rel_left, rel_right) -> (o, lse, o_lo)
@@ -23,6 +25,7 @@ Every op fails loudly (SteError) without the HIP library; there is no CPU implem
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -53,6 +56,23 @@ def fbank(wav: Tensor, lengths: Tensor, t_max: int, pad_value: float = 1.0, mask
 @fbank.register_fake
 def _fbank_fake(wav, lengths, t_max, pad_value=1.0, mask_mode=0):
     return wav.new_empty(wav.shape[0], t_max, 160, dtype=F32), wav.new_empty(wav.shape[0], t_max, dtype=torch.int64)
+
+
+# --------------------------------------------------------------------- resample
+@torch.library.custom_op("ste::resample", mutates_args=())
+def resample(wav: Tensor, lengths: Tensor, sr_in: int, sr_out: int = 16000) -> tuple[Tensor, Tensor]:
+    wav, lengths = wav.float().contiguous(), lengths.to(torch.int32).contiguous()
+    if sr_in == sr_out:   # a custom op may not return its inputs: copies here, ops.resample returns them as they are
+        return wav.clone(), lengths.clone()
+    return ops.resample(wav, lengths, int(sr_in), int(sr_out))
+
+
+@resample.register_fake
+def _resample_fake(wav, lengths, sr_in, sr_out=16000):
+    g = math.gcd(sr_in, sr_out)
+    M, L = sr_in // g, sr_out // g
+    return (wav.new_empty(wav.shape[0], (wav.shape[1] * L + M - 1) // M, dtype=F32),
+            wav.new_empty(wav.shape[0], dtype=torch.int32))
 
 
 # ----------------------------------------------------------------------- linear
@@ -241,4 +261,4 @@ def _adamw_fake(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, s
     return None
 
 
-OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_")
+OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample")

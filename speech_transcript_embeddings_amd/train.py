@@ -663,11 +663,17 @@ class TrainStep:
         lengths = lengths.to(device=wav.device, dtype=torch.int32, non_blocking=True)
         return ops.fbank(wav, lengths, T, pad_value=self.pad_value, mask_mode=0)
 
-    def __call__(self, wav, lengths, ids_pos, mask_pos, ids_neg, mask_neg):
+    def __call__(self, wav, lengths, ids_pos, mask_pos, ids_neg, mask_neg, sampling_rate=None):
         """One micro-batch from raw 16 kHz waveforms (GPU fbank first).  lengths on the host (as a
         DataLoader delivers them) also give SpecAugment its per-clip frame counts with no
-        device->host sync; on the device they are read back only if SpecAugment is on."""
+        device->host sync; on the device they are read back only if SpecAugment is on.
+        sampling_rate: the clips' native rate when it is not 16 kHz; they are resampled on the GPU
+        first (ops.resample), for the fbank and the wav2vec2 route alike."""
         host = lengths.tolist() if lengths.device.type == "cpu" else None
+        if sampling_rate is not None and int(sampling_rate) != 16000:
+            wav, lengths = ops.resample(wav, lengths.to(device=wav.device, dtype=torch.int32), int(sampling_rate))
+            if host is not None:
+                host = [ops.resampled_length(n, sampling_rate) for n in host]
         feats, amask = self.features(wav, lengths)
         batch = {"input_ids_pos": ids_pos, "attention_mask_pos": mask_pos, "input_ids_neg": ids_neg,
                  "attention_mask_neg": mask_neg, "input_values": feats, "attention_mask_audio": amask}
