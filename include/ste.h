@@ -668,6 +668,40 @@ int ste_w2v_ln_gelu_bwd(const void* dh, int dh_bf16, const void* z, const float*
                         const float* gamma, const float* beta, int64_t rows, int C, void* dz, float* dgamma,
                         float* dbeta, float* dbias, float* work, int64_t work_floats, void* stream);
 
+/* -------------------------------------------------------------- retrieval --
+ * Search of an embedding corpus (the use of ref:processor.py:128-146's get_text_embedding /
+ * get_audio_embedding vectors; the reference itself only compares pairs): per query the k best
+ * corpus rows by dot product, without writing the Q x N score matrix.
+ * Order: value descending, then index ascending (total, deterministic).  Scores are fp32 fmaf
+ * chains over k = 0.. on the f32 MFMA, bit-identical to ste_similarity's and independent of tile,
+ * split and chunk.  Inputs are assumed finite.
+ *
+ * ste_topk_sim: q fp32 [Q,P]; corpus [N,P] fp32, or bf16 if corpus_bf16 (widened on load, exact);
+ *   1 <= k <= 128, P <= 1024 (else STE_ERR_SHAPE), index_base >= 0 is added to every returned index.
+ *   values fp32 [Q,k], indices int32 [Q,k]; with N < k the tail is (-inf, -1).
+ *   target (optional, int32 [Q], global ids, -1 = none) asks for rank int32 [Q]: the number of
+ *   corpus rows that order before the target row (0-based rank; -1 for no target).  tscore
+ *   (optional, fp32 [Q]) is the target's score when the target lies outside this corpus chunk
+ *   (from ste_topk_target_score on the chunk that holds it); without tscore the target's score is
+ *   computed here and a target outside [index_base, index_base + N) counts as none.
+ *   splits: 0 = automatic, else the number of corpus slices (clamped to the tile count); ws holds
+ *   at least ste_topk_sim_plan's ws_bytes.
+ * ste_topk_sim_plan (host only, no launch): the split count used and the workspace bytes:
+ *   Q*8 (target scratch) + for splits > 1 the partial lists and counts, Q*splits*(8k + 4).
+ * ste_topk_target_score: tscore[q] = <q_q, corpus[target[q] - index_base]> for the targets inside
+ *   this chunk; other entries are left as they are.
+ * ste_topk_merge: candidates vals / idx [Q, C] (C = L*k for L lists, sorted or not; idx -1 =
+ *   empty) -> the k first under the same order, [Q,k]; counts (optional, int32 [Q, L]) are summed
+ *   into out_rank [Q] (-1 if any is -1). */
+int ste_topk_sim_plan(int Q, int N, int P, int k, int splits, int* splits_out, int64_t* ws_bytes);
+int ste_topk_sim(const float* q, const void* corpus, int corpus_bf16, int Q, int N, int P, int k, int index_base,
+                 const int32_t* target, const float* tscore, int splits, float* values, int32_t* indices,
+                 int32_t* rank, void* ws, int64_t ws_bytes, void* stream);
+int ste_topk_target_score(const float* q, const void* corpus, int corpus_bf16, int Q, int N, int P, int index_base,
+                          const int32_t* target, float* tscore, void* stream);
+int ste_topk_merge(const float* vals, const int32_t* idx, int Q, int C, int k, const int32_t* counts, int L,
+                   float* out_v, int32_t* out_i, int32_t* out_rank, void* stream);
+
 const char* ste_version(void);
 
 #ifdef __cplusplus

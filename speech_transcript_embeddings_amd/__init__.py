@@ -9,3 +9,5 @@ every hot op a hand-written HIP kernel in libste.so (include/ste.h).
 __version__ = "0.2.0"
 
 from . import torch_ops  # noqa: E402,F401  (torch.ops.ste.* custom operators)
+from .retrieval import (EmbeddingIndex, embed_audio, embed_texts, evaluate_retrieval,  # noqa: E402,F401
+                        retrieval_metrics)

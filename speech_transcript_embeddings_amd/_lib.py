@@ -258,6 +258,13 @@ _SIGS = {
     "ste_w2v_ln_gelu_work": (c_int64, [c_int64, c_int]),
     "ste_w2v_ln_gelu_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ste_topk_sim_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int64)]),
+    "ste_topk_sim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                             c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ste_topk_target_score": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                      c_void_p]),
+    "ste_topk_merge": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p]),
     "ste_version": (C.c_char_p, []),
 }
 

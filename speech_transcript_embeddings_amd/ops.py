@@ -711,6 +711,74 @@ def similarity(a, t, S):
     call("ste_similarity", ptr(a), ptr(t), a.shape[0], t.shape[0], a.shape[1], ptr(S), _s())
 
 
+def topk_sim_plan(Q, N, P, k, splits=0):
+    """(splits used, workspace bytes) of topk_sim at this shape (ste_topk_sim_plan, host only)."""
+    s, b = C.c_int(), C.c_int64()
+    call("ste_topk_sim_plan", int(Q), int(N), int(P), int(k), int(splits), C.byref(s), C.byref(b))
+    return s.value, b.value
+
+
+def _corpus(corpus, P):
+    if corpus.dtype not in (F32, BF16):
+        raise TypeError(f"corpus must be fp32 or bf16, got {corpus.dtype}")
+    if corpus.dim() != 2 or corpus.shape[1] != P or not corpus.is_contiguous():
+        raise ValueError(f"corpus must be contiguous [N, {P}], got {tuple(corpus.shape)}")
+    return int(corpus.dtype == BF16)
+
+
+def topk_sim(q, corpus, k, *, index_base=0, target=None, tscore=None, splits=0):
+    """The k best corpus rows per query by dot product (ste_topk_sim), the Q x N scores never
+    written.  q fp32 [Q, P], corpus fp32 or bf16 [N, P] -> (values fp32 [Q, k], indices int32
+    [Q, k]) ordered by value descending then index ascending, index_base added to the indices.
+    With target (int32 [Q], global ids, -1 = none) also ranks int32 [Q]: the rows ordering before
+    the target; tscore fp32 [Q] carries the score of a target that lies in another chunk."""
+    Q, P = q.shape
+    assert q.dtype == F32 and q.is_contiguous()
+    bf = _corpus(corpus, P)
+    N = corpus.shape[0]
+    _, ws_bytes = topk_sim_plan(Q, N, P, k, splits)
+    dev = q.device
+    values = torch.empty(Q, k, device=dev, dtype=F32)
+    indices = torch.empty(Q, k, device=dev, dtype=torch.int32)
+    ranks = None
+    if target is not None:
+        assert target.dtype == torch.int32 and target.shape == (Q,) and target.is_contiguous()
+        assert tscore is None or (tscore.dtype == F32 and tscore.shape == (Q,) and tscore.is_contiguous())
+        ranks = torch.empty(Q, device=dev, dtype=torch.int32)
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    call("ste_topk_sim", ptr(q), ptr(corpus), bf, Q, N, P, int(k), int(index_base), ptr(target), ptr(tscore),
+         int(splits), ptr(values), ptr(indices), ptr(ranks), ptr(ws), ws_bytes, _s())
+    return (values, indices) if ranks is None else (values, indices, ranks)
+
+
+def topk_target_score(q, corpus, target, tscore, *, index_base=0):
+    """tscore[i] = <q_i, corpus[target[i] - index_base]> for the targets inside this chunk, by
+    the arithmetic of topk_sim's scan; the other entries of tscore are left alone."""
+    Q, P = q.shape
+    bf = _corpus(corpus, P)
+    call("ste_topk_target_score", ptr(q), ptr(corpus), bf, Q, corpus.shape[0], P, int(index_base), ptr(target),
+         ptr(tscore), _s())
+    return tscore
+
+
+def topk_merge(values, indices, k, counts=None):
+    """Merge candidate lists: values / indices [Q, C] (any order, index -1 = empty) -> the k first
+    by value descending then index ascending, [Q, k].  counts int32 [Q, L] (per-list rank counts)
+    -> also their sum int32 [Q] (-1 where any is -1)."""
+    Q, Cn = values.shape
+    assert values.dtype == F32 and indices.dtype == torch.int32 and indices.shape == values.shape
+    values, indices = values.contiguous(), indices.contiguous()
+    ov = torch.empty(Q, k, device=values.device, dtype=F32)
+    oi = torch.empty(Q, k, device=values.device, dtype=torch.int32)
+    ranks, L = None, 0
+    if counts is not None:
+        assert counts.dtype == torch.int32 and counts.shape[0] == Q
+        counts, L = counts.contiguous(), counts.shape[1]
+        ranks = torch.empty(Q, device=values.device, dtype=torch.int32)
+    call("ste_topk_merge", ptr(values), ptr(indices), Q, Cn, int(k), ptr(counts), L, ptr(ov), ptr(oi), ptr(ranks), _s())
+    return (ov, oi) if ranks is None else (ov, oi, ranks)
+
+
 def pair_loss_fwd(S, off_neg, align, B, L, tau, aw, gamma, s_pos, s_neg, loss):
     call("ste_pair_loss_fwd", ptr(S), _ld(S), off_neg, ptr(align), B, L, float(tau), float(aw), float(gamma),
          ptr(s_pos), ptr(s_neg), ptr(loss), _s())

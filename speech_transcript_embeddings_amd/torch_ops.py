@@ -20,6 +20,8 @@ through them); the fused training step itself calls the C ABI directly (engine.p
         AlignmentAwareInfoNCE (ref :702-742)
     ste::adamw_(p!, g, m!, v!, p_bf16!, lr, beta1, beta2, eps, weight_decay, step, sumsq?, max_norm)
         AdamW.step with clip_grad_norm_'s coefficient folded in (ref :1108-1110)
+    ste::topk_sim(q, corpus, k) -> (values, indices)
+        the k best corpus rows per query by dot product (retrieval over processor.py:128-146's embeddings)
 
 Every op fails loudly (SteError) without the HIP library; there is no CPU implementation.
 """
@@ -261,4 +263,20 @@ def _adamw_fake(p, g, m, v, p_bf16, lr, beta1, beta2, eps, weight_decay, step, s
     return None
 
 
-OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample")
+# --------------------------------------------------------------------- retrieval
+@torch.library.custom_op("ste::topk_sim", mutates_args=())
+def topk_sim(q: Tensor, corpus: Tensor, k: int) -> tuple[Tensor, Tensor]:
+    """The k best corpus rows per query by dot product: q [Q, P], corpus [N, P] (fp32 or bf16) ->
+    (values fp32 [Q, k], indices int32 [Q, k]), value descending then index ascending."""
+    corpus = corpus.contiguous()
+    if corpus.dtype not in (BF16, F32):
+        corpus = corpus.float()
+    return ops.topk_sim(q.float().contiguous(), corpus, int(k))
+
+
+@topk_sim.register_fake
+def _topk_sim_fake(q, corpus, k):
+    return q.new_empty(q.shape[0], k, dtype=F32), q.new_empty(q.shape[0], k, dtype=torch.int32)
+
+
+OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim")
