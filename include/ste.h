@@ -413,6 +413,28 @@ int ste_xattn_fwd(const float* q, const void* k, const void* v, int64_t ldkv, co
 int ste_xattn_bwd(const float* q, const void* k, const void* v, int64_t ldkv, const float* probs, const float* dout,
                   const int32_t* mask, int B, int S, int P, int nh, int nq, float scale, float drop_p,
                   uint64_t seed0, uint64_t seed1, float* dq, float* dk, float* dv, int64_t lddkv, void* stream);
+/* Forward-only cross attention for reranking (no dropout, no probs): the shape rule of ste_xattn_fwd
+ * without its cap on S (P <= 1024, P % nh == 0, dh = P/nh a multiple of 8 and <= 256), ldkv >= P, ldkv % 8 == 0,
+ * k / v / out 16-B aligned; any violation returns STE_ERR_SHAPE before a launch.  A masked key scores
+ * -1e9 (a fully masked clip averages all S value rows); mask NULL = every key valid.
+ *
+ * ste_xattn_mq_fwd: C queries per clip against that clip's keys/values.  q fp32 [U,P]; qrow int32
+ *   [B*C]: slot (b,c) uses row qrow[b*C+c] of q, -1 = empty slot (its out row is zeros); k, v bf16,
+ *   row b*S+s, row stride ldkv; mask int32 [B*S]; out fp32 [B*C,P]; C >= 1, S unbounded.  Online
+ *   softmax over 32-key tiles on the bf16 MFMA: the query enters as bf16 hi + lo (scores at
+ *   fp32-q x bf16-k precision), the probabilities are rounded once to bf16 for P·V, sums are fp32.
+ *   Elementwise |out - exact| <= 2^-8 · sum_s p_s·|v_s| for |q|, |k| <= 1.  The key tiles are split
+ *   over a block's waves by S alone and folded in a fixed order: out of slot (b,c) is bit-identical
+ *   whatever C, B, the slot's position and the other slots are.
+ * ste_xattn_gather_fwd: pair r attends with row qrow[r] of q (fp32 [*,P]) over block kvblk[r] of k / v /
+ *   mask (rows kvblk[r]*S + s); out fp32 [R,P]; a negative qrow[r] or kvblk[r] writes a zero row.
+ *   S <= 16384 and fewer than 2^31 rows of k / v in all.  The arithmetic of ste_xattn1_fwd at drop_p = 0: bitwise equal to it on replicated
+ *   inputs. */
+int ste_xattn_mq_fwd(const float* q, const int32_t* qrow, const void* k, const void* v, int64_t ldkv,
+                     const int32_t* mask, int B, int C, int S, int P, int nh, float scale, float* out, void* stream);
+int ste_xattn_gather_fwd(const float* q, const int32_t* qrow, const void* k, const void* v, int64_t ldkv,
+                         const int32_t* kvblk, const int32_t* mask, int R, int S, int P, int nh, float scale,
+                         float* out, void* stream);
 /* As ste_xattn_bwd, but dk/dv are bf16 and WRITTEN (not accumulated), and colsum_part fp32
  * [B, 2P] receives per-sample column sums of dk (cols [0,P)) and dv (cols [P,2P)) in fp32, for the
  * key/value bias gradient; lddkv % 8 == 0. */

@@ -10,4 +10,4 @@ __version__ = "0.2.0"
 
 from . import torch_ops  # noqa: E402,F401  (torch.ops.ste.* custom operators)
 from .retrieval import (EmbeddingIndex, embed_audio, embed_texts, evaluate_retrieval,  # noqa: E402,F401
-                        retrieval_metrics)
+                        plan_candidates, rerank, rerank_order, reranked_ranks, retrieval_metrics)

@@ -183,6 +183,10 @@ _SIGS = {
     "ste_xattn_bwd_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int,
                                    c_int, c_int, c_int, c_int, c_float, c_float, c_uint64, c_uint64, c_void_p,
                                    c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "ste_xattn_mq_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int,
+                                 c_int, c_int, c_float, c_void_p, c_void_p]),
+    "ste_xattn_gather_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int,
+                                     c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     "ste_align_attn_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                    c_float, c_uint64, c_void_p, c_void_p, c_int64, c_void_p]),
     "ste_align_attn_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int,

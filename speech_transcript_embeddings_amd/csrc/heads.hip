@@ -6,11 +6,13 @@
 // These are small (rows = batch), latency-bound kernels; the big sequence-length
 // projections around them run through ste_gemm.
 #include "common.h"
+#include "xattn_fwd.h"
 #include "../../include/ste.h"
 
 namespace {
 
 constexpr int NT = 256;
+static_assert(NT == XATTN_NT, "ste_xattn_fwd launches xattn_fwd_kernel with NT threads");
 
 STE_DEV float block_sum(float v, float* red) {
   v = wave_sum(v);
@@ -292,107 +294,8 @@ __global__ __launch_bounds__(NT) void weighted_pool_bwd_kernel(const float* weig
   }
 }
 
-// ---------------------------------------------------- single-query cross attention
-// scores/probs layout: [B][nh][S]
-// CrossModalAttention with NQ single-vector queries per sample sharing the same keys/values
-// (the positive and the corrupted transcript's text->audio calls, ref:525-542, read one audio
-// K/V): one block per (sample, head), so B*nh blocks fill the chip.  Query qi of sample b is
-// row qi*B + b of q / out / dout / dq and of the probs ((qi*B + b)*nh + head)*S; its dropout
-// uses seed qi and the index (b*nh + head)*S + s (the per-call layout of one query set).
-// Rows of K/V are read with 16-B (8 x bf16) loads; the PV / dK / dV passes put 4 columns on a
-// lane and spread the key rows over the block's row groups.
-template <int NQ>
-__global__ __launch_bounds__(NT) void xattn_fwd_kernel(const float* q, const bf16* k, const bf16* v, int64_t ldkv,
-                                                     const int32_t* mask, int B, int S, int P, int nh, float scale,
-                                                     float drop_p, uint64_t seed0, uint64_t seed1, float* probs,
-                                                     float* out) {
-  extern __shared__ float sp[];  // NQ * S
-  __shared__ float sq[NQ][256];
-  __shared__ float red[NQ][NT / 64];
-  __shared__ f32x4 racc[NT];
-  const int b = blockIdx.x, hh = blockIdx.y, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int dh = P / nh, c0 = hh * dh;
-  for (int c = tid; c < NQ * dh; c += NT) sq[c / dh][c % dh] = q[(int64_t)((c / dh) * B + b) * P + c0 + c % dh];
-  __syncthreads();
-  // scores
-  for (int s = tid; s < S; s += NT) {
-    const bf16* kr = k + (int64_t)(b * S + s) * ldkv + c0;
-    float acc[NQ];
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) acc[qi] = 0.f;
-    for (int d = 0; d < dh; d += 8) {
-      const bf16x8 x = *reinterpret_cast<const bf16x8*>(kr + d);
-#pragma unroll
-      for (int e = 0; e < 8; ++e)
-#pragma unroll
-        for (int qi = 0; qi < NQ; ++qi) acc[qi] += (float)x[e] * sq[qi][d + e];
-    }
-    const bool masked = mask && mask[b * S + s] == 0;
-#pragma unroll
-    for (int qi = 0; qi < NQ; ++qi) sp[qi * S + s] = masked ? -1e9f : acc[qi] * scale;
-  }
-  __syncthreads();
-  // softmax per query over the block
-  float mx[NQ], sm[NQ];
-#pragma unroll
-  for (int qi = 0; qi < NQ; ++qi) {
-    float m = -INFINITY;
-    for (int s = tid; s < S; s += NT) m = fmaxf(m, sp[qi * S + s]);
-    m = wave_max(m);
-    if (lane == 0) red[qi][w] = m;
-  }
-  __syncthreads();
-#pragma unroll
-  for (int qi = 0; qi < NQ; ++qi) {
-    mx[qi] = fmaxf(fmaxf(red[qi][0], red[qi][1]), fmaxf(red[qi][2], red[qi][3]));
-    float t = 0.f;
-    for (int s = tid; s < S; s += NT) t += __expf(sp[qi * S + s] - mx[qi]);
-    sm[qi] = wave_sum(t);
-  }
-  __syncthreads();
-#pragma unroll
-  for (int qi = 0; qi < NQ; ++qi)
-    if (lane == 0) red[qi][w] = sm[qi];
-  __syncthreads();
-  const uint32_t thresh = (uint32_t)(drop_p * 4294967296.0);
-  const float inv_keep = drop_p > 0.f ? 1.f / (1.f - drop_p) : 1.f;
-#pragma unroll
-  for (int qi = 0; qi < NQ; ++qi) {
-    const float inv = 1.f / (red[qi][0] + red[qi][1] + red[qi][2] + red[qi][3]);
-    const uint64_t sd = qi ? seed1 : seed0;
-    float* pr = probs + ((int64_t)(qi * B + b) * nh + hh) * S;
-    for (int s = tid; s < S; s += NT) {
-      float pv = __expf(sp[qi * S + s] - mx[qi]) * inv;
-      pr[s] = pv;
-      if (drop_p > 0.f) pv *= drop_scale(sd, ((uint64_t)b * nh + hh) * S + s, thresh, inv_keep);
-      sp[qi * S + s] = pv;
-    }
-  }
-  __syncthreads();
-  // out = P·V: lane (row group rg, column quad cq)
-  const int nq4 = dh >> 2, RG = NT / nq4;
-  const int cq = tid % nq4, rg = tid / nq4;
-  f32x4 acc[NQ];
-#pragma unroll
-  for (int qi = 0; qi < NQ; ++qi) acc[qi] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (rg < RG)
-    for (int s = rg; s < S; s += RG) {
-      const f32x4 vv = load_bf16x4(v + (int64_t)(b * S + s) * ldkv + c0 + 4 * cq);
-#pragma unroll
-      for (int qi = 0; qi < NQ; ++qi) acc[qi] += vv * sp[qi * S + s];
-    }
-#pragma unroll
-  for (int qi = 0; qi < NQ; ++qi) {
-    racc[tid] = acc[qi];
-    __syncthreads();
-    if (tid < nq4) {
-      f32x4 t = racc[tid];
-      for (int r = 1; r < RG; ++r) t += racc[r * nq4 + tid];
-      *reinterpret_cast<f32x4*>(out + (int64_t)(qi * B + b) * P + c0 + 4 * tid) = t;
-    }
-    __syncthreads();
-  }
-}
+// single-query cross attention forward: xattn_fwd_kernel<NQ, GATHER> lives in xattn_fwd.h (shared with
+// xattn_mq.hip); scores/probs layout [B][nh][S]
 
 // OUT_BF16 = false: dk, dv are fp32 and ACCUMULATED (+=) once for all NQ queries.
 // OUT_BF16 = true:  dk, dv are bf16 and WRITTEN (the block is their only writer), and the fp32
@@ -846,11 +749,13 @@ extern "C" int ste_xattn_fwd(const float* q, const void* k, const void* v, int64
     return STE_ERR_SHAPE;
   const size_t lds = (size_t)nq * S * sizeof(float);
   if (nq == 1)
-    hipLaunchKernelGGL(xattn_fwd_kernel<1>, dim3(B, nh), dim3(NT), lds, (hipStream_t)stream, q, (const bf16*)k,
-                       (const bf16*)v, ldkv, mask, B, S, P, nh, scale, drop_p, seed0, seed1, probs, out);
+    hipLaunchKernelGGL((xattn_fwd_kernel<1, false>), dim3(B, nh), dim3(NT), lds, (hipStream_t)stream, q,
+                       (const bf16*)k, (const bf16*)v, ldkv, mask, B, S, P, nh, scale, drop_p, seed0, seed1, probs,
+                       out, nullptr, nullptr);
   else
-    hipLaunchKernelGGL(xattn_fwd_kernel<2>, dim3(B, nh), dim3(NT), lds, (hipStream_t)stream, q, (const bf16*)k,
-                       (const bf16*)v, ldkv, mask, B, S, P, nh, scale, drop_p, seed0, seed1, probs, out);
+    hipLaunchKernelGGL((xattn_fwd_kernel<2, false>), dim3(B, nh), dim3(NT), lds, (hipStream_t)stream, q,
+                       (const bf16*)k, (const bf16*)v, ldkv, mask, B, S, P, nh, scale, drop_p, seed0, seed1, probs,
+                       out, nullptr, nullptr);
   STE_CHECK_LAUNCH();
   return 0;
 }

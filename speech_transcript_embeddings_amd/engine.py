@@ -1187,6 +1187,83 @@ class Engine:
         sv = dict(b=b, L=L, T=T, thb=thb, ahb=ahb, aseqb=aseqb, tseqb=tseqb, tx=tx, ax=ax, tf=tf, af=af)
         return tfused, afused, sv
 
+    @torch.no_grad()
+    def score_pairs(self, tproj, th, tmask, aproj, ah, amask, candidates, audio_context=None):
+        """The fused pair score the model is trained on (ref:525-563; cv_inference.py:148-161), for
+        C candidate transcripts per clip: text [U,P] + hidden [U,L,Ht] + mask [U,L] (the DISTINCT
+        transcripts), audio [B,P] + hidden [B,T,Ha] + mask, candidates int [B,C] with values in
+        [-1, U) -> scores fp32 [B,C], -inf for an empty (-1) slot.
+
+        The audio K/V is projected once per clip and the text K/V once per distinct transcript;
+        slot (b, c)'s text query attends over clip b's audio (xattn_mq_fwd, queries gathered in the
+        kernel) and clip b's audio query over transcript candidates[b, c] (xattn_gather_fwd).
+        audio_context=None is the pair form (each pair's audio embedding is fused with its own
+        candidate); audio_context=j fuses every row's audio with column j's transcript, which with
+        candidates [clean, corrupted] and j = 0 is the training forward's (s_pos, s_neg).  Without
+        use_cross_modal the score is the cosine of the projections.  Inference arithmetic (no
+        dropout), nothing saved.  Scores come from the fp32 MFMA chain of topk_target_score."""
+        m, dev = self.m, self.s.device
+        U, L, Ht = th.shape
+        B, T, Ha = ah.shape
+        P = m.projection_dim
+        cand = candidates.to(dev, torch.int32).contiguous()
+        if cand.dim() != 2 or cand.shape[0] != B or cand.shape[1] < 1:
+            raise ValueError(f"candidates must be [{B}, C >= 1], got {tuple(cand.shape)}")
+        C = cand.shape[1]
+        lo, hi = (int(x) for x in torch.stack((cand.min(), cand.max())).tolist())
+        if lo < -1 or hi >= U:
+            raise ValueError(f"candidates must lie in [-1, {U}), got [{lo}, {hi}]")
+        if audio_context is not None and not 0 <= int(audio_context) < C:
+            raise ValueError(f"audio_context must be a column of candidates, got {audio_context}")
+        R = B * C
+        slot = cand.view(-1)
+        tproj, aproj = tproj.float().contiguous(), aproj.float().contiguous()
+        scores = torch.full((R,), float("-inf"), device=dev, dtype=F32)
+
+        def unit(x):
+            y = self._e(*x.shape)
+            ops.l2norm_fwd(x, y, self._e(x.shape[0]))
+            return y
+
+        arep = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(C)   # clip of each pair
+        if not m.use_cross_modal:
+            ops.topk_target_score(unit(aproj).index_select(0, arep.long()), unit(tproj), slot, scores)
+            return scores.view(B, C)
+        nh = m.xattn_heads
+        thb = ops.cast_bf16(th.contiguous(), self._e(U * L, Ht, dtype=BF16))
+        ahb = ops.cast_bf16(ah.contiguous(), self._e(B * T, Ha, dtype=BF16))
+        tm32 = self._mask32(tmask, U * L) if tmask is not None else None
+        if amask is not None and self.raw_audio and amask.shape[-1] != T:
+            from .wav2vec2 import frame_mask   # a sample-level wav2vec2 mask, as in cross_forward
+            am32 = frame_mask(self.acfg, amask, B, amask.shape[-1], T, dev)[1]
+        else:
+            am32 = self._mask32(amask, B * T) if amask is not None else None
+        kva, _ = self._kv("text_to_audio_attention", "audio_seq_to_projection", ahb)    # once per clip
+        kvt, _ = self._kv("audio_to_text_attention", "text_seq_to_projection", thb)     # once per transcript
+        s = self.s
+        qt = ops.linear(tproj, self._w32("text_to_audio_attention.query.weight"),
+                        s.p("text_to_audio_attention.query.bias"))
+        qa = ops.linear(aproj, self._w32("audio_to_text_attention.query.weight"),
+                        s.p("audio_to_text_attention.query.bias"))
+        # the transcript each pair's audio attends over; a pair is empty when either side is
+        ctx_t = slot if audio_context is None else cand[:, int(audio_context)].repeat_interleave(C)
+        kvblk = torch.where(slot < 0, slot, ctx_t).contiguous()
+        live = torch.where(kvblk < 0, kvblk, torch.arange(R, device=dev, dtype=torch.int32))
+        tcat, acat = self._e(R, 2 * P), self._e(R, 2 * P)
+        att = self._e(R, P)
+        ops.xattn_mq_fwd(qt, slot, kva[:, :P], kva[:, P:], am32, B, C, T, nh, att)
+        ops.linear(att, self._w32("text_to_audio_attention.out_proj.weight"),
+                   s.p("text_to_audio_attention.out_proj.bias"), out=tcat[:, P:])
+        ops.copy2d(tcat[:, :P], tproj.index_select(0, slot.clamp(min=0).long()))
+        ops.xattn_gather_fwd(qa, arep, kvt[:, :P], kvt[:, P:], kvblk, tm32, R, L, nh, att)
+        ops.linear(att, self._w32("audio_to_text_attention.out_proj.weight"),
+                   s.p("audio_to_text_attention.out_proj.bias"), out=acat[:, P:])
+        ops.copy2d(acat[:, :P], aproj.index_select(0, arep.long()))
+        tfused, _ = self._fuse_fwd("text_fusion", tcat)
+        afused, _ = self._fuse_fwd("audio_fusion", acat)
+        ops.topk_target_score(unit(afused), unit(tfused), live, scores)
+        return scores.view(B, C)
+
     def cross_backward(self, sv, d_tf, d_af):
         """-> (d text_projected [b,P], d text_hidden [b*L,Ht], d audio_projected [b,P],
         d audio_hidden [b*T,Ha]) fp32; parameter gradients += into the flat gradient buffer."""

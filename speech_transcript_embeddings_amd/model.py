@@ -280,6 +280,30 @@ class EnhancedAudioTextModel(nn.Module):
         return _CrossFn.apply(self, text_projected, text_hidden, text_mask, audio_projected, audio_hidden, audio_mask,
                               self.store.master[:1].detach().requires_grad_(True))
 
+    @torch.no_grad()
+    def score_candidates(self, input_values, attention_mask_audio, input_ids, attention_mask, candidates,
+                         audio_context=None, text_batch=256, audio_encoded=None):
+        """The fused pair score (the one the loss trains, ref:525-563) of C candidate transcripts per
+        clip -> fp32 [B, C], -inf for an empty slot.  input_ids / attention_mask [U, L] are the
+        DISTINCT transcripts and candidates int [B, C] indexes them (-1 = empty): one audio-encoder
+        pass per clip and one text-encoder pass per distinct transcript (in chunks of text_batch
+        rows), then Engine.score_pairs.  audio_encoded: the (projection, hidden) pair of an
+        encode_audio call already made on these clips in eval mode, to skip the audio pass.
+        Forward only, inference arithmetic."""
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        was_training, self.training = self.training, False   # encode_* read the flag: no dropout here
+        try:
+            aproj, ah = audio_encoded or self.encode_audio(input_values, attention_mask_audio)
+            parts = [self.encode_text(input_ids[i:i + text_batch], attention_mask[i:i + text_batch])
+                     for i in range(0, input_ids.shape[0], text_batch)]
+        finally:
+            self.training = was_training
+        tproj, th = (torch.cat([p[j] for p in parts]) for j in (0, 1)) if len(parts) > 1 else parts[0]
+        self.store.sync_shadow()
+        return self.engine.score_pairs(tproj, th, attention_mask, aproj, ah, attention_mask_audio, candidates,
+                                       audio_context)
+
     def _encode_nograd(self, kind, x, mask):
         self.store.sync_shadow()
         e = self.engine

@@ -660,6 +660,30 @@ def xattn_fwd(q, k, v, mask, B, S, nh, probs, out, seeds, drop_p=0.0):
          float(drop_p), int(seeds[0]) & (2**64 - 1), int(seeds[-1]) & (2**64 - 1), ptr(probs), ptr(out), _s())
 
 
+def xattn_mq_fwd(q, qrow, k, v, mask, B, C, S, nh, out):
+    """C queries per clip sharing the clip's K/V (forward only): slot (b, c) attends with row
+    qrow[b*C + c] of q [U, P] (-1: empty slot, zero row) over rows b*S.. of k / v; out fp32 [B*C, P]."""
+    P = q.shape[-1]
+    assert q.dtype == F32 and q.is_contiguous() and qrow.dtype == torch.int32 and qrow.numel() == B * C
+    assert k.dtype == BF16 and v.dtype == BF16 and _ld(k) == _ld(v) and k.shape[0] >= B * S
+    assert out.dtype == F32 and out.is_contiguous() and out.shape == (B * C, P)
+    assert mask is None or (mask.dtype == torch.int32 and mask.numel() == B * S)
+    call("ste_xattn_mq_fwd", ptr(q), ptr(qrow), ptr(k), ptr(v), _ld(k), ptr(mask), B, C, S, P, nh,
+         float((P // nh) ** -0.5), ptr(out), _s())
+
+
+def xattn_gather_fwd(q, qrow, k, v, kvblk, mask, R, S, nh, out):
+    """Pair r attends with row qrow[r] of q over block kvblk[r] (rows kvblk[r]*S..) of k / v / mask;
+    a negative entry writes a zero row.  Bitwise xattn1_fwd(drop_p=0) on the replicated operands."""
+    P = q.shape[-1]
+    assert q.dtype == F32 and q.is_contiguous() and out.dtype == F32 and out.shape == (R, P) and out.is_contiguous()
+    assert qrow.dtype == torch.int32 and kvblk.dtype == torch.int32 and qrow.numel() == R and kvblk.numel() == R
+    assert k.dtype == BF16 and v.dtype == BF16 and _ld(k) == _ld(v)
+    assert mask is None or mask.dtype == torch.int32
+    call("ste_xattn_gather_fwd", ptr(q), ptr(qrow), ptr(k), ptr(v), _ld(k), ptr(kvblk), ptr(mask), R, S, P, nh,
+         float((P // nh) ** -0.5), ptr(out), _s())
+
+
 def xattn_bwd(q, k, v, probs, dout, B, S, nh, dq, dk, dv, seeds, drop_p=0.0, colsum=None, mask=None):
     """dk/dv fp32: accumulated (+=).  dk/dv bf16: written (ste_xattn_bwd_bf16), and the fp32
     column sums of [dk | dv] are added into colsum [2P] when given."""

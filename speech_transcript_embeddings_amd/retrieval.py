@@ -12,6 +12,15 @@ where does its transcript rank among all transcripts of the split, and the rever
     retrieval_metrics(ranks, ks)                         -> recall@k, mrr, median_rank, n
     evaluate_retrieval(model, data_loader, device, ks)   -> {"a2t": metrics, "t2a": metrics}
 
+Stage 2 rescores a clip's k retrieved transcripts with the fused pair score the model is
+trained on (model.score_candidates: one audio pass per clip, one text pass per distinct candidate):
+
+    plan_candidates(idx)                          -> (unique ids [U], slots [Q, k] into them)
+    rerank_order(scores, idx)                     -> (values, indices), score descending
+    reranked_ranks(first_ranks, idx, order, tgt)  -> the target's rank after reranking
+    rerank(model, input_values, attention_mask_audio, text_ids, text_mask, idx) -> (values, indices)
+    evaluate_retrieval(..., rerank_k=k)           -> also "a2t_rerank"
+
 Scores and selection run in ste_topk_sim (csrc/retrieval.hip): the queries x corpus score matrix
 is never written.  The order is total (value descending, index ascending) and a row's score is
 bit-identical wherever it is computed, so results do not depend on how the corpus was chunked.
@@ -128,22 +137,96 @@ def retrieval_metrics(ranks: torch.Tensor, ks=(1, 5, 10)) -> dict:
     return out
 
 
+# ------------------------------------------------------------------- stage 2: rerank
+def plan_candidates(idx: torch.Tensor):
+    """Candidate lists idx [Q, k] (corpus ids, -1 = empty) -> (unique ids [U] ascending, slots [Q, k]
+    with idx == unique[slots] and -1 kept as -1), so that each distinct candidate is encoded once.
+    Pure torch, any device."""
+    idx = torch.as_tensor(idx)
+    valid = idx >= 0
+    unique = torch.unique(idx[valid])
+    slots = torch.searchsorted(unique, idx.clamp(min=0).contiguous()).to(idx.dtype)
+    return unique, torch.where(valid, slots, torch.full_like(slots, -1))
+
+
+def rerank_order(scores: torch.Tensor, idx: torch.Tensor):
+    """Reorder candidate lists idx [Q, k] by scores [Q, k]: score descending, ties by stage-1
+    position ascending (a total order), empty slots (idx < 0) last as (-inf, -1).  Returns
+    (values [Q, k], indices [Q, k]) like EmbeddingIndex.search.  Pure torch, any device."""
+    idx = torch.as_tensor(idx)
+    empty = idx < 0
+    s = torch.where(empty, torch.full_like(scores, float("-inf")), scores)
+    order = torch.sort(s, dim=1, descending=True, stable=True)[1]
+    # empties after every real candidate, whatever its score: a second stable sort on the flag
+    order = order.gather(1, torch.sort(empty.gather(1, order).to(torch.int8), dim=1, stable=True)[1])
+    return s.gather(1, order), torch.where(empty, torch.full_like(idx, -1), idx).gather(1, order)
+
+
+def reranked_ranks(first_ranks: torch.Tensor, idx: torch.Tensor, order_indices: torch.Tensor,
+                   targets: torch.Tensor) -> torch.Tensor:
+    """The target's 0-based rank after reranking the k first candidates idx [Q, k] into
+    order_indices [Q, k]: its position in the reranked list if it is among them, else its stage-1
+    rank first_ranks [Q] (reranking permutes the first k places only, so recall@m for m >= k
+    cannot change).  targets < 0 (no target) keep first_ranks.  Pure torch, any device."""
+    tgt = torch.as_tensor(targets).to(order_indices.dtype).reshape(-1, 1)
+    among = ((torch.as_tensor(idx) == tgt) & (tgt >= 0)).any(1)
+    pos = ((order_indices == tgt) & (tgt >= 0)).to(torch.int8).argmax(1)
+    return torch.where(among, pos.to(first_ranks.dtype), first_ranks)
+
+
+@torch.no_grad()
+def rerank(model, input_values, attention_mask_audio, text_ids, text_mask, idx, *, audio_encoded=None):
+    """Rerank each clip's retrieved transcripts idx [B, k] (rows of the token store text_ids /
+    text_mask [N, L], as returned by a text index's search) with the fused pair score:
+    plan_candidates -> gather the distinct rows -> model.score_candidates -> rerank_order.
+    Returns (values fp32 [B, k], indices [B, k]).  audio_encoded: see score_candidates."""
+    unique, slots = plan_candidates(idx)
+    if unique.numel() == 0:
+        return rerank_order(torch.zeros(idx.shape, device=idx.device, dtype=F32), idx)
+    rows = unique.to(text_ids.device, torch.int64)
+    scores = model.score_candidates(input_values, attention_mask_audio, text_ids.index_select(0, rows),
+                                    text_mask.index_select(0, rows), slots, audio_encoded=audio_encoded)
+    return rerank_order(scores, idx.to(scores.device))
+
+
+def _pad_rows(chunks, fill):
+    """Concatenate [n_i, L_i] chunks, right-padded to the longest L with fill."""
+    L = max(c.shape[1] for c in chunks)
+    return torch.cat([torch.nn.functional.pad(c, (0, L - c.shape[1]), value=fill) for c in chunks])
+
+
 @torch.no_grad()
 def evaluate_retrieval(model, data_loader, device, ks=(1, 5, 10), index_dtype: torch.dtype = F32,
-                       return_ranks: bool = False) -> dict:
+                       return_ranks: bool = False, rerank_k: int = 0) -> dict:
     """One pass over a loader of the reference's batch dicts (custom_collate_fn's keys): embeds the
     clean transcripts and the audio, indexes both and ranks pair i's partner for query i in both
     directions.  Returns {"a2t": retrieval_metrics, "t2a": retrieval_metrics} (audio -> text,
     text -> audio), plus the rank tensors under "a2t_ranks" / "t2a_ranks" on request.  None
     batches are skipped, as evaluate() does; everything stays on the device until the metrics are
-    read."""
+    read.
+
+    rerank_k > 0 with a use_cross_modal model adds "a2t_rerank" (and "a2t_rerank_ranks"): the first
+    pass also keeps the clean transcripts' token ids and masks on the device (right-padded to the
+    longest L with the pad id and mask 0, which leaves a transcript's states unchanged), and the
+    loader is iterated a SECOND time: per batch the audio is encoded once, its rerank_k best
+    transcripts are searched and reranked with the fused pair score (rerank), and the pair's rank
+    becomes its position in that list when it is among them.  The second pass must yield the same
+    items in the same order (a loader with shuffle=False over a deterministic dataset); each
+    batch's input_ids_pos is compared with the stored rows and a mismatch raises ValueError.
+    Out of scope: reranking text -> audio (it needs the audio states of arbitrary corpus clips),
+    the model_infer.py variant, a cache of the corpus text K/V, and any backward."""
     model.eval()
-    texts, audios = [], []
+    do_rerank = rerank_k > 0 and getattr(model, "use_cross_modal", False)
+    texts, audios, tok_ids, tok_mask = [], [], [], []
     text_index = audio_index = None
+
+    def on_device(batch):
+        return {k: v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
+
     for batch in data_loader:
         if batch is None:
             continue
-        b = {k: v.to(device, non_blocking=True) if isinstance(v, torch.Tensor) else v for k, v in batch.items()}
+        b = on_device(batch)
         t = embed_texts(model, b["input_ids_pos"], b["attention_mask_pos"])
         a = embed_audio(model, b["input_values"], b.get("attention_mask_audio"))
         if text_index is None:
@@ -153,6 +236,9 @@ def evaluate_retrieval(model, data_loader, device, ks=(1, 5, 10), index_dtype: t
         audio_index.add(a)
         texts.append(t)
         audios.append(a)
+        if do_rerank:
+            tok_ids.append(b["input_ids_pos"])
+            tok_mask.append(b["attention_mask_pos"])
     if text_index is None:
         a2t = t2a = torch.empty(0, dtype=torch.int64)
     else:
@@ -162,4 +248,35 @@ def evaluate_retrieval(model, data_loader, device, ks=(1, 5, 10), index_dtype: t
     out = {"a2t": retrieval_metrics(a2t, ks), "t2a": retrieval_metrics(t2a, ks)}
     if return_ranks:
         out.update(a2t_ranks=a2t, t2a_ranks=t2a)
+    if not do_rerank:
+        return out
+    reranked = [a2t[:0]]
+    if text_index is not None:
+        ids = _pad_rows(tok_ids, model.text_cfg.pad_token_id)
+        mask = _pad_rows(tok_mask, 0)
+        n, at = len(text_index), 0
+        for batch in data_loader:
+            if batch is None:
+                continue
+            b = on_device(batch)
+            bi = b["input_ids_pos"]
+            nb, Lb = bi.shape
+            if at + nb > n or Lb > ids.shape[1] or not torch.equal(bi, ids[at:at + nb, :Lb]) \
+                    or bool(mask[at:at + nb, Lb:].any()):
+                raise ValueError("evaluate_retrieval(rerank_k>0): the loader's second pass differs from its first "
+                                 f"at items {at}..{at + nb - 1}; it must yield the same items in the same order "
+                                 "(shuffle=False)")
+            am = b.get("attention_mask_audio")
+            enc = model.encode_audio(b["input_values"], am)
+            idx = text_index.search(_unit_rows(enc[0]), rerank_k)[1]
+            order = rerank(model, b["input_values"], am, ids, mask, idx, audio_encoded=enc)[1]
+            tgt = torch.arange(at, at + nb, device=idx.device, dtype=idx.dtype)
+            reranked.append(reranked_ranks(a2t[at:at + nb], idx, order, tgt))
+            at += nb
+        if at != n:
+            raise ValueError(f"evaluate_retrieval(rerank_k>0): the second pass yielded {at} items, the first {n}")
+    rr = torch.cat(reranked)
+    out["a2t_rerank"] = retrieval_metrics(rr, ks)
+    if return_ranks:
+        out["a2t_rerank_ranks"] = rr
     return out

@@ -22,6 +22,8 @@ through them); the fused training step itself calls the C ABI directly (engine.p
         AdamW.step with clip_grad_norm_'s coefficient folded in (ref :1108-1110)
     ste::topk_sim(q, corpus, k) -> (values, indices)
         the k best corpus rows per query by dot product (retrieval over processor.py:128-146's embeddings)
+    ste::xattn_mq(q, qrow, k, v, mask?, C, nh) -> out
+        CrossModalAttention core (ref :125-168) for C candidate queries per clip sharing its keys/values
 
 Every op fails loudly (SteError) without the HIP library; there is no CPU implementation.
 """
@@ -279,4 +281,25 @@ def _topk_sim_fake(q, corpus, k):
     return q.new_empty(q.shape[0], k, dtype=F32), q.new_empty(q.shape[0], k, dtype=torch.int32)
 
 
-OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim")
+@torch.library.custom_op("ste::xattn_mq", mutates_args=())
+def xattn_mq(q: Tensor, qrow: Tensor, k: Tensor, v: Tensor, mask: Optional[Tensor], C: int, nh: int) -> Tensor:
+    """C single-vector queries per clip against that clip's keys/values (forward only): q [U, P],
+    qrow int [B*C] (row of q per slot, -1 = empty slot -> zero row), k / v [B*S, P] (bf16, or fp32
+    cast to bf16), mask int [B*S] (0 = masked key) or None -> out fp32 [B*C, P]."""
+    B = qrow.numel() // int(C)
+    if B * int(C) != qrow.numel() or B == 0 or k.shape[0] % B or k.shape != v.shape:
+        raise ValueError(f"xattn_mq: qrow of {qrow.numel()} slots, C = {C}, k {tuple(k.shape)}, v {tuple(v.shape)}")
+    P = q.shape[-1]
+    out = torch.empty(B * int(C), P, device=q.device, dtype=F32)
+    m32 = None if mask is None else mask.reshape(-1).to(torch.int32).contiguous()
+    ops.xattn_mq_fwd(q.float().contiguous(), qrow.reshape(-1).to(torch.int32).contiguous(), _bf16(k), _bf16(v), m32,
+                     B, int(C), k.shape[0] // B, int(nh), out)
+    return out
+
+
+@xattn_mq.register_fake
+def _xattn_mq_fake(q, qrow, k, v, mask, C, nh):
+    return q.new_empty(qrow.numel(), q.shape[-1], dtype=F32)
+
+
+OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim", "xattn_mq")
