@@ -108,8 +108,36 @@ int ste_gemm_tile_map(int t, int num_m, int num_n, int* tm, int* tn);
  * 470-477), computed in fp32 as the reference does.  KC operands need K % 4 == 0 and
  * ld % 4 == 0, KM operands (M or N) % 4 == 0; A, B 16-B aligned; batch 1.  A weight gradient
  * (plain epilogue, fp32 C) with K >= 1024 whose tiles cannot fill the chip is split along K
- * into slabs of ws (when given) summed in slab order. */
+ * into slabs of ws (when given) summed in slab order.
+ * A launch with at most ste_gemm_f32_plan_small_tiles 64x64 output tiles and no column sums runs
+ * on 32x32 tiles instead: more workgroups, the same value for every output element.
+ * Optional few-tile split, off by default because it changes the fp32 summation order (at most
+ * ste_gemm_f32_plan_max_tiles 64x64 tiles, K >= 512; any layout and any epilogue): given ws, K is split into S slabs of whole 16-deep chunks, slab z =
+ * [z*kc, min(K, (z+1)*kc)), whose raw accumulators go to ws[z][M][N]; a second kernel adds them in
+ * increasing z and applies the epilogue (same results and dropout mask as one launch, up to fp32
+ * summation order; run-to-run deterministic).  Column sums of such a launch are always the ordered
+ * plan: their 2*ceil(M/64) partial rows of N floats follow the S slabs in ws.  A ws smaller than
+ * ste_gemm_f32_ws_floats lowers S (down to one launch); it never fails the call. */
 int ste_gemm_f32(const ste_gemm_args* args, void* stream);
+/* Host-only plan queries of ste_gemm_f32 (no launch, no GPU needed).  _plan: the number of
+ * K-slabs S these args run as (1: a single launch), given their ws / ws_bytes.  _plan_slab: the
+ * slab length kc of that plan (a multiple of 16; K when S = 1).  _ws_floats: the workspace, in
+ * floats, with which the launch gets the S its shape wants: S*M*N for the slabs (nothing when the
+ * shape is not split) plus the ordered column-sum rows (2*ceil(M/64)*N with colsum). */
+int ste_gemm_f32_plan(const ste_gemm_args* args);
+int ste_gemm_f32_plan_slab(const ste_gemm_args* args);
+int64_t ste_gemm_f32_ws_floats(const ste_gemm_args* args);
+/* The output tile edge of the (unsplit) launch of these args: 32 or 64. */
+int ste_gemm_f32_plan_tile(const ste_gemm_args* args);
+/* Plan threshold (process-wide atomic, host-only): the most 64x64 output tiles for which
+ * ste_gemm_f32 takes the few-tile split (default 0: off).  0 disables it: ste_gemm_f32 then plans as
+ * it did without that split (the plain weight-gradient split included), which gives tests and A/B
+ * runs the single-launch result from the same library.  Returns the previous value.  Read once per
+ * call, when that call is planned; meant for test set-up, not for tuning a running step. */
+int ste_gemm_f32_plan_max_tiles(int tiles);
+/* The same for the 32x32 tiling: the most 64x64 output tiles for which a launch without column
+ * sums takes it (default 64; 0: every launch on 64x64 tiles).  Returns the previous value. */
+int ste_gemm_f32_plan_small_tiles(int tiles);
 
 /* Which kernel ste_gemm would launch for these args (no launch, host-only):
  * STE_GEMM_KERNEL_SMALL (the 128x128 kernel), _8PH (the persistent 8-phase kernel) or _SPLITK

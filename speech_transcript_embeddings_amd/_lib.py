@@ -122,6 +122,12 @@ class AttnArgs(C.Structure):
 _SIGS = {
     "ste_gemm": (c_int, [C.POINTER(GemmArgs), c_void_p]),
     "ste_gemm_f32": (c_int, [C.POINTER(GemmArgs), c_void_p]),
+    "ste_gemm_f32_plan": (c_int, [C.POINTER(GemmArgs)]),
+    "ste_gemm_f32_plan_slab": (c_int, [C.POINTER(GemmArgs)]),
+    "ste_gemm_f32_ws_floats": (c_int64, [C.POINTER(GemmArgs)]),
+    "ste_gemm_f32_plan_max_tiles": (c_int, [c_int]),
+    "ste_gemm_f32_plan_small_tiles": (c_int, [c_int]),
+    "ste_gemm_f32_plan_tile": (c_int, [C.POINTER(GemmArgs)]),
     "ste_gemm_kernel": (c_int, [C.POINTER(GemmArgs)]),
     "ste_gemm_colsum_ws_floats": (c_int64, [C.POINTER(GemmArgs)]),
     "ste_gemm_tile_map": (c_int, [c_int, c_int, c_int, C.POINTER(c_int), C.POINTER(c_int)]),

@@ -112,7 +112,13 @@ def gemm(a, b, *, a_kc=True, b_kc=True, M=None, N=None, K=None, out=None, out_bf
         args.row_scale = ptr(row_scale)
     args.alpha, args.beta, args.act = float(alpha), float(beta), int(act)
     args.drop_p, args.seed, args.drop_ld = float(drop_p), int(seed) & (2**64 - 1), int(drop_ld)
-    if colsum is not None and mx8 is None and not ATOMIC_SUMS:
+    if f32 and not (colsum is not None and ATOMIC_SUMS):
+        # the ordered column-sum rows and, when the optional few-tile split is on
+        # (ste_gemm_f32_plan_max_tiles), its K-slabs: the library's plan says how much workspace it wants
+        need = int(fn("ste_gemm_f32_ws_floats")(C.byref(args)))
+        if need and (ws is None or ws.numel() < need):
+            ws = stream_ws(a.device, need, "red", floor=1 << 20)
+    elif colsum is not None and mx8 is None and not ATOMIC_SUMS:
         # deterministic bias gradients: the ordered partial-sum plan needs a workspace this large
         need = int(fn("ste_gemm_colsum_ws_floats")(C.byref(args)))
         if ws is None or ws.numel() < need:
