@@ -488,6 +488,39 @@ int ste_align_attn_bwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv,
  * dw[k] += Σ_m a[m] z[m][k], db += Σ_m a[m]  (z = the activation OUTPUT for RELU/TANH). */
 int ste_rank1_bwd(const float* a, const float* w, const void* z, int M, int K, int act, void* out, float* dw,
                   float* db, void* stream);
+/* The inference form of ste_align_attn_fwd (same q / kv / kmask operands, no dropout, no probs):
+ * what WordLevelAlignmentModule.forward returns besides the confidence, the head-averaged
+ * alignment_matrix (ref:training/trainer_unfreeze.py:295, alignment_weights.mean(dim=1)).  A block
+ * owns 8 queries and loops over all heads with the running head sum in LDS, so per-head
+ * probabilities never reach HBM.  Each output is optional (all three NULL: STE_ERR_ARG) and its
+ * bits do not depend on which others are requested:
+ *   matrix fp32 [B, L, T] = (Σ_h softmax_t(q_h·k_h/√d)[l][t]) · (1/nh), heads added in the order
+ *     h = 0..nh-1 and multiplied once; a masked key is exactly 0;
+ *   emit fp32 [B, T, lde] (lde >= L), FRAME-major: emit[b][t][l] = log(max(matrix[b][l][t], FLT_MIN)),
+ *     finite everywhere; columns l >= L of a row are not written (the input of ste_align_decode);
+ *   out bf16 [B*L, ldo]: the attention output, bitwise ste_align_attn_fwd's at drop_p = 0.
+ * T <= 2048 (16·T·4 B of dynamic LDS on top of 8 KiB static, checked against the device's
+ * per-block limit), d = P/nh <= 256, d % 8 == 0, B <= 65535; otherwise STE_ERR_SHAPE before a
+ * launch.  A clip without a valid key is outside the contract. */
+int ste_align_matrix_fwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const int32_t* kmask, int B, int L,
+                         int T, int P, int nh, float* matrix, float* emit, int64_t lde, void* out, int64_t ldo,
+                         void* stream);
+/* Monotone (Viterbi) decode of frame-major emissions emit fp32 [B, T, lde] into one frame span per
+ * token.  Pair b has tokens 0..n-1 (n = ntok[b]) and frames 0..F-1 (F = nfrm[b]); the path l(t)
+ * maximises Σ_t emit[b][t][l(t)] under l(0) = 0, l(F-1) = n-1, l(t) - l(t-1) in {0, 1}.  The
+ * arithmetic is fixed, one fp32 add per cell:
+ *   D_0[0] = e[0][0], D_0[l>0] = -inf;
+ *   D_t[l] = (D_{t-1}[l-1] > D_{t-1}[l] ? D_{t-1}[l-1] : D_{t-1}[l]) + e[t][l]
+ * (the path advances only on a strict improvement), and the walk back starts from (F-1, n-1).
+ * spans int32 [B, L, 2] = (first frame, last frame + 1) for l < n, (-1, -1) for n <= l < L;
+ * score fp32 [B] = D_{F-1}[n-1].  A pair with n < 1, n > L, F < n or F > T is infeasible: spans all
+ * (-1, -1), score -inf, no error.  One wave per pair, no workspace, no atomics: a pair's result does
+ * not depend on B or on the other pairs.  L <= 256, T <= 2048, lde >= L, else STE_ERR_SHAPE; a NULL
+ * pointer is STE_ERR_ARG; both before a launch.  Columns l >= L of emit never affect the result
+ * (with lde % 4 == 0 up to three of them are read along with a row's last tokens).  Columns l < L
+ * are assumed free of NaN and +inf (-inf is allowed). */
+int ste_align_decode(const float* emit, int64_t lde, const int32_t* ntok, const int32_t* nfrm, int B, int L, int T,
+                     int32_t* spans, float* score, void* stream);
 
 /* ------------------------------------------------------------------- loss --
  * F.normalize(p=2, dim=1, eps=1e-12) rows (ref:training/trainer_unfreeze.py:561-563). */

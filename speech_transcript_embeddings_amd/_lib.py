@@ -198,6 +198,10 @@ _SIGS = {
     "ste_align_attn_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int,
                                    c_int, c_int, c_int, c_float, c_uint64, c_void_p, c_void_p, c_int64, c_void_p,
                                    c_int64, c_void_p]),
+    "ste_align_matrix_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int,
+                                     c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
+    "ste_align_decode": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                 c_void_p]),
     "ste_rank1_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
     "ste_l2norm_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

@@ -4,8 +4,9 @@ ref = /root/reference/training/trainer_unfreeze.py:214-310, invoked at :550-558 
 positive transcript: text/audio projections -> 4-head text->audio attention with the
 audio key-padding mask -> out_proj -> LN(text_hidden + output_projection(.)) ->
 confidence MLP (Linear -> ReLU -> Linear) -> scores * text_mask = model.last_alignment_scores
-(fed to AlignmentAwareInfoNCE's per-sample weighting, ref:730-734).  The head-averaged
-alignment matrix the reference computes is never used, so it is not materialised.
+(fed to AlignmentAwareInfoNCE's per-sample weighting, ref:730-734).  The training path never
+uses the head-averaged alignment matrix the reference also returns, so it does not materialise it;
+the forward-only route align_infer does (ste_align_matrix_fwd), for model.align's word timestamps.
 """
 from __future__ import annotations
 
@@ -48,6 +49,64 @@ def align_forward(eng, th, thb_pos, ahb, b, L, T, ctx, train, seed, hs):
     hs["align"] = dict(tp=tp, ap=ap, q=q, kv=kv, probs=probs, att=att, o2=o2, y=y, st=st, aligned_b=aligned_b, c1=c1,
                        tmask=tmask, p=p_drop, seed=seed, b=b, L=L, T=T, nh=nh)
     return scores.view(b, L)
+
+
+def align_infer(eng, th, thb, ahb, b, L, T, ctx, *, want_matrix=False, want_emit=True):
+    """The forward-only route: align_forward's eval arithmetic with the attention on
+    ste_align_matrix_fwd, which also gives what the reference's forward returns next to the
+    confidence — the head-averaged alignment matrix (ref:295) — and its frame-major log for
+    ops.align_decode.  No [b, nh, L, T] probabilities buffer is allocated.
+    -> (scores fp32 [b, L], matrix fp32 [b, L, T] or None, emit fp32 [b, T, L] or None)."""
+    s = eng.s
+    m = eng.m
+    P = m.projection_dim
+    nh = m.word_level_alignment.num_heads
+    W = s.w(PRE + "alignment_attention.in_proj_weight")
+    bW = s.p(PRE + "alignment_attention.in_proj_bias")
+    tp = ops.linear(thb, s.w(PRE + "text_projection.weight"), s.p(PRE + "text_projection.bias"), out_bf16=True)
+    ap = ops.linear(ahb, s.w(PRE + "audio_projection.weight"), s.p(PRE + "audio_projection.bias"), out_bf16=True)
+    q = ops.linear(tp, W[:P], bW[:P], out_bf16=True)
+    kv = ops.linear(ap, W[P:], bW[P:], out_bf16=True)
+    matrix = eng._e(b, L, T) if want_matrix else None
+    emit = eng._e(b, T, L) if want_emit else None
+    att = eng._e(b * L, P, dtype=BF16)
+    ops.align_matrix_fwd(q, kv, ctx["a_mask32"], b, L, T, nh, matrix=matrix, emit=emit, out=att)
+    o2 = ops.linear(att, s.w(PRE + "alignment_attention.out_proj.weight"),
+                    s.p(PRE + "alignment_attention.out_proj.bias"), out_bf16=True)
+    y = ops.linear(o2, s.w(PRE + "output_projection.weight"), s.p(PRE + "output_projection.bias"),
+                   residual=th[: b * L])
+    aligned_b = eng._e(b * L, P, dtype=BF16)
+    eng._ln(y, PRE + "layer_norm", 1e-5, yb=aligned_b)
+    c1 = ops.linear(aligned_b, s.w(PRE + "alignment_confidence.0.weight"), s.p(PRE + "alignment_confidence.0.bias"),
+                    act=ACT_RELU, out_bf16=True)
+    tmask = eng._e(b * L)
+    _lib.call("ste_mask_i64_to_f32", ctx["_tmask_i64"].data_ptr(), tmask.data_ptr(), None, b * L, _lib.stream_ptr())
+    scores = ops.linear(c1, s.w(PRE + "alignment_confidence.2.weight"), s.p(PRE + "alignment_confidence.2.bias"),
+                        row_scale=tmask)
+    return scores.view(b, L), matrix, emit
+
+
+def words_from_tokens(token_spans, token_scores, word_ids):
+    """Token spans -> word spans, on the tensors' device (plain torch scatter-reduce).
+    token_spans int [B, L, 2] ((-1, -1) for a token without a span), token_scores [B, L], word_ids
+    int [B, L] as a fast tokenizer's word_ids() gives them, -1 for special and padding tokens.
+    -> (word_spans int32 [B, W, 2], word_scores fp32 [B, W]), W = max word id + 1: a word's span is
+    the min start to the max end over its tokens, its score the mean of their confidences; a word
+    id no token carries gives (-1, -1) and score 0."""
+    B, L = word_ids.shape
+    wid = word_ids.to(token_spans.device, torch.int64)
+    W = max(int(wid.max().item()) + 1, 0) if wid.numel() else 0
+    start, end = token_spans[..., 0].to(torch.int64), token_spans[..., 1].to(torch.int64)
+    valid = (wid >= 0) & (start >= 0)
+    idx = torch.where(valid, wid, torch.full_like(wid, W))          # everything else to a spare column
+    big = torch.iinfo(torch.int32).max
+    ws = torch.full((B, W + 1), big, dtype=torch.int64, device=wid.device).scatter_reduce(1, idx, start, "amin")
+    we = torch.full((B, W + 1), -1, dtype=torch.int64, device=wid.device).scatter_reduce(1, idx, end, "amax")
+    cnt = torch.zeros(B, W + 1, dtype=F32, device=wid.device).scatter_add(1, idx, valid.to(F32))
+    tot = torch.zeros(B, W + 1, dtype=F32, device=wid.device).scatter_add(1, idx, token_scores.to(F32) * valid)
+    live = cnt[:, :W] > 0
+    spans = torch.stack([torch.where(live, ws[:, :W], -1), torch.where(live, we[:, :W], -1)], -1).to(torch.int32)
+    return spans, torch.where(live, tot[:, :W] / cnt[:, :W].clamp(min=1), 0.0)
 
 
 def align_backward(eng, d_align, hs, ctx, dth, dah):

@@ -1293,6 +1293,64 @@ class Engine:
         from .align import align_backward
         align_backward(self, d_align, hs, ctx, dth, dah)
 
+    @property
+    def frame_seconds(self):
+        """Seconds per encoder frame: two stacked fbank hops (w2v-bert), or the conv stack's total
+        stride in samples (wav2vec2), at 16 kHz — 0.02 for both families."""
+        from .features import HOP, SAMPLE_RATE, STACK
+        samples = math.prod(self.acfg.conv_stride) if self.raw_audio else HOP * STACK
+        return samples / SAMPLE_RATE
+
+    @torch.no_grad()
+    def align_pairs(self, th, tmask, ah, amask, word_ids=None, return_matrix=False):
+        """Word timestamps from the alignment head: clip b against transcript b, text
+        hidden [B,L,Ht] + mask [B,L], audio hidden [B,T,Ha] + mask (frames, or wav2vec2 samples; None
+        = every frame valid).  align_infer gives the confidence, the head-mean alignment matrix and its
+        frame-major log; ops.align_decode turns that into one frame span per token over the pair's
+        ntok = Σ text mask tokens and nfrm = Σ frame mask frames.  Both masks must be prefix masks
+        (checked on the device, one sync).  Inference arithmetic, nothing saved.  -> dict, see
+        EnhancedAudioTextModel.align."""
+        from .align import align_infer, words_from_tokens
+        dev = self.s.device
+        B, L, Ht = th.shape
+        T, Ha = ah.shape[1], ah.shape[2]
+        if ah.shape[0] != B:
+            raise ValueError(f"align pairs clip b with transcript b: {ah.shape[0]} clips, {B} transcripts")
+        tm = (torch.ones(B, L, dtype=torch.int64, device=dev) if tmask is None
+              else tmask.to(dev, torch.int64).contiguous())
+        if amask is not None and self.raw_audio and amask.shape[-1] != T:
+            from .wav2vec2 import frame_mask   # a sample-level wav2vec2 mask, as in cross_forward
+            am32 = frame_mask(self.acfg, amask, B, amask.shape[-1], T, dev)[1]
+        else:
+            am32 = self._mask32(amask, B * T) if amask is not None else None
+        bad = (tm[:, 1:] > tm[:, :-1]).any()
+        if am32 is not None:
+            fm = am32.view(B, T)
+            bad = bad | ((fm[:, 1:] != 0) & (fm[:, :-1] == 0)).any()
+        if bool(bad):
+            raise ValueError("align needs prefix masks (right-padded transcripts and clips)")
+        ntok = (tm != 0).sum(1, dtype=torch.int32)
+        nfrm = (torch.full((B,), T, dtype=torch.int32, device=dev) if am32 is None
+                else (am32.view(B, T) != 0).sum(1, dtype=torch.int32))
+        thf = th.reshape(B * L, Ht).float().contiguous()
+        thb = ops.cast_bf16(thf, self._e(B * L, Ht, dtype=BF16))
+        ahb = ops.cast_bf16(ah.reshape(B * T, Ha).float().contiguous(), self._e(B * T, Ha, dtype=BF16))
+        scores, matrix, emit = align_infer(self, thf, thb, ahb, B, L, T, {"a_mask32": am32, "_tmask_i64": tm},
+                                           want_matrix=return_matrix, want_emit=True)
+        spans, path = ops.align_decode(emit, ntok, nfrm)
+        fs = self.frame_seconds
+
+        def seconds(sp):
+            return torch.where(sp < 0, -1.0, sp.float() * fs)
+
+        out = dict(token_spans=spans, token_seconds=seconds(spans), scores=scores, path_score=path)
+        if return_matrix:
+            out["matrix"] = matrix
+        if word_ids is not None:
+            ws, wsc = words_from_tokens(spans, scores, word_ids.to(dev))
+            out.update(word_spans=ws, word_seconds=seconds(ws), word_scores=wsc)
+        return out
+
     # ============================================================== full step
     def forward(self, batch, train: bool, save: bool = True):
         """compute_pos_neg_embeddings (ref:502-565) -> (tp_fused, tn_fused, a_fused, align, ctx).

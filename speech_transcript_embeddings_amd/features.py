@@ -24,6 +24,7 @@ from . import ops
 
 SAMPLE_RATE = 16000
 FRAME, HOP = 400, 160
+STACK = 2   # fbank frames stacked per encoder frame (the extractor's stride)
 
 
 def num_frames(n_samples: int) -> int:
@@ -53,9 +54,9 @@ class SeamlessM4TFeatureExtractor:
 
     model_input_names = ["input_features", "attention_mask"]
 
-    def __init__(self, feature_size=80, num_mel_bins=80, padding_value=1.0, sampling_rate=SAMPLE_RATE, stride=2,
+    def __init__(self, feature_size=80, num_mel_bins=80, padding_value=1.0, sampling_rate=SAMPLE_RATE, stride=STACK,
                  device=None):
-        if (feature_size, num_mel_bins, sampling_rate, stride) != (80, 80, SAMPLE_RATE, 2):
+        if (feature_size, num_mel_bins, sampling_rate, stride) != (80, 80, SAMPLE_RATE, STACK):
             raise ValueError("only the w2v-bert-2.0 front end (80 mel bins, 16 kHz, stride 2) is implemented")
         self.feature_size, self.num_mel_bins, self.stride = feature_size, num_mel_bins, stride
         self.padding_value, self.sampling_rate = float(padding_value), sampling_rate

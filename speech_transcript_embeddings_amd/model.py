@@ -304,6 +304,40 @@ class EnhancedAudioTextModel(nn.Module):
         return self.engine.score_pairs(tproj, th, attention_mask, aproj, ah, attention_mask_audio, candidates,
                                        audio_context)
 
+    @torch.no_grad()
+    def align(self, input_values, attention_mask_audio, input_ids, attention_mask=None, *, word_ids=None,
+              audio_encoded=None, text_encoded=None, return_matrix=False):
+        """Where in clip b is each token of transcript b, and how confident is the alignment head
+        about it (WordLevelAlignmentModule, ref:214-310; needs use_word_alignment, else ValueError).
+        One clip is paired with one transcript.  The head-averaged text->audio attention matrix
+        (ref:295) is decoded on the GPU into the monotone path that gives every token of the
+        transcript at least one frame and tiles the clip's valid frames (Engine.align_pairs).  The
+        <s> and </s> tokens take part in the decode: they absorb leading and trailing silence, so
+        the first word starts where <s> ends.  Both masks must be prefix masks (right padding), else
+        ValueError.  audio_encoded / text_encoded: the (projection, hidden) pairs of encode_audio /
+        encode_text calls already made on these inputs in eval mode, to skip those passes.
+        Forward only, inference arithmetic (the training flag is forced off and restored).
+
+        Returns a dict: token_spans int32 [B, L, 2] in frames, (first, last + 1), (-1, -1) for padding;
+        token_seconds fp32 [B, L, 2] = spans x engine.frame_seconds (-1 kept); scores fp32 [B, L], the
+        per-token confidence (the meaning of last_alignment_scores); path_score fp32 [B], the
+        path's summed log alignment weight; matrix fp32 [B, L, T] with return_matrix=True; and with
+        word_ids (int [B, L], a fast tokenizer's word_ids(), -1 for special and padding tokens)
+        word_spans / word_seconds [B, W, 2] and word_scores [B, W], W = max word id + 1: min start to
+        max end and the mean confidence over a word's tokens, (-1, -1) for an unused word id."""
+        if not self.use_word_alignment:
+            raise ValueError("align() needs a model built with use_word_alignment=True")
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        was_training, self.training = self.training, False   # encode_* read the flag: no dropout here
+        try:
+            _, ah = audio_encoded or self.encode_audio(input_values, attention_mask_audio)
+            _, th = text_encoded or self.encode_text(input_ids, attention_mask)
+        finally:
+            self.training = was_training
+        self.store.sync_shadow()
+        return self.engine.align_pairs(th, attention_mask, ah, attention_mask_audio, word_ids, return_matrix)
+
     def _encode_nograd(self, kind, x, mask):
         self.store.sync_shadow()
         e = self.engine

@@ -724,6 +724,37 @@ def align_attn_bwd(q, kv, probs, dout, B, L, T, nh, dsbuf, dq, dkv, drop_p=0.0, 
          float(drop_p), int(seed) & (2**64 - 1), ptr(dsbuf), ptr(dq), _ld(dq), ptr(dkv), _ld(dkv), _s())
 
 
+def align_matrix_fwd(q, kv, kmask, B, L, T, nh, *, matrix=None, emit=None, out=None):
+    """The inference form of align_attn_fwd (ste_align_matrix_fwd): any of matrix fp32 [B, L, T]
+    (head mean of the probabilities), emit fp32 [B, T, lde >= L] (its frame-major log, the input of
+    align_decode) and out bf16 [B*L, ldo] (the attention output); per-head probabilities are not
+    written."""
+    P = kv.shape[-1] // 2
+    assert q.dtype == BF16 and kv.dtype == BF16 and q.shape[0] >= B * L and kv.shape[0] >= B * T
+    assert kmask is None or (kmask.dtype == torch.int32 and kmask.numel() == B * T)
+    assert matrix is None or (matrix.dtype == F32 and matrix.is_contiguous() and matrix.numel() == B * L * T)
+    assert emit is None or (emit.dtype == F32 and emit.shape[:2] == (B, T) and emit.stride(2) == 1
+                            and emit.stride(0) == T * emit.stride(1))
+    assert out is None or (out.dtype == BF16 and out.shape[0] >= B * L)
+    call("ste_align_matrix_fwd", ptr(q), _ld(q), ptr(kv), _ld(kv), ptr(kmask), B, L, T, P, nh, ptr(matrix), ptr(emit),
+         0 if emit is None else emit.stride(1), ptr(out), 0 if out is None else _ld(out), _s())
+
+
+def align_decode(emit, ntok, nfrm):
+    """Monotone (Viterbi) decode of frame-major emissions (ste_align_decode): emit fp32 [B, T, L]
+    (a column view of a wider [B, T, lde] buffer is fine), ntok / nfrm int32 [B] -> (spans int32
+    [B, L, 2] as (first frame, last frame + 1), -1 beyond a pair's tokens; score fp32 [B], the
+    path's sum)."""
+    B, T, L = emit.shape
+    assert emit.dtype == F32 and emit.stride(2) == 1 and emit.stride(0) == T * emit.stride(1)
+    assert ntok.dtype == torch.int32 and nfrm.dtype == torch.int32 and ntok.numel() == B and nfrm.numel() == B
+    assert ntok.is_contiguous() and nfrm.is_contiguous()
+    spans = torch.empty(B, L, 2, device=emit.device, dtype=torch.int32)
+    score = torch.empty(B, device=emit.device, dtype=F32)
+    call("ste_align_decode", ptr(emit), emit.stride(1), ptr(ntok), ptr(nfrm), B, L, T, ptr(spans), ptr(score), _s())
+    return spans, score
+
+
 def rank1_bwd(a, w, z, act, out, dw=None, db=None):
     M, K = z.shape
     call("ste_rank1_bwd", ptr(a), ptr(w), ptr(z), M, K, int(act), ptr(out), ptr(dw), ptr(db), _s())

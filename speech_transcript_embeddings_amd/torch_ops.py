@@ -24,6 +24,10 @@ through them); the fused training step itself calls the C ABI directly (engine.p
         the k best corpus rows per query by dot product (retrieval over processor.py:128-146's embeddings)
     ste::xattn_mq(q, qrow, k, v, mask?, C, nh) -> out
         CrossModalAttention core (ref :125-168) for C candidate queries per clip sharing its keys/values
+    ste::align_matrix(q, kv, kmask?, nh) -> (matrix, emit, out)
+        WordLevelAlignmentModule's head-averaged alignment_matrix (ref :295), its frame-major log, the output
+    ste::align_decode(emit, ntok, nfrm) -> (spans, score)
+        monotone (Viterbi) decode of that log matrix into one frame span per token
 
 Every op fails loudly (SteError) without the HIP library; there is no CPU implementation.
 """
@@ -302,4 +306,47 @@ def _xattn_mq_fake(q, qrow, k, v, mask, C, nh):
     return q.new_empty(qrow.numel(), q.shape[-1], dtype=F32)
 
 
-OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim", "xattn_mq")
+# -------------------------------------------------------------------- alignment
+@torch.library.custom_op("ste::align_matrix", mutates_args=())
+def align_matrix(q: Tensor, kv: Tensor, kmask: Optional[Tensor], nh: int) -> tuple[Tensor, Tensor, Tensor]:
+    """q [B, L, P], kv [B, T, 2P] = [K | V] (bf16, or fp32 cast to bf16), kmask int [B, T] (0 = padded
+    frame) or None -> (matrix fp32 [B, L, T], the head mean of softmax(q_h·k_h/√d); emit fp32
+    [B, T, L] = log(max(matrix, FLT_MIN)) frame-major; out bf16 [B, L, P], the attention output).
+    Forward only."""
+    B, L, P = q.shape
+    T = kv.shape[1]
+    if kv.shape[0] != B or kv.shape[2] != 2 * P:
+        raise ValueError(f"align_matrix: q {tuple(q.shape)}, kv {tuple(kv.shape)}")
+    matrix = torch.empty(B, L, T, device=q.device, dtype=F32)
+    emit = torch.empty(B, T, L, device=q.device, dtype=F32)
+    out = torch.empty(B * L, P, device=q.device, dtype=BF16)
+    km = None if kmask is None else kmask.reshape(-1).to(torch.int32).contiguous()
+    ops.align_matrix_fwd(_bf16(q.reshape(B * L, P)), _bf16(kv.reshape(B * T, 2 * P)), km, B, L, T, int(nh),
+                         matrix=matrix, emit=emit, out=out)
+    return matrix, emit, out.view(B, L, P)
+
+
+@align_matrix.register_fake
+def _align_matrix_fake(q, kv, kmask, nh):
+    B, L, P = q.shape
+    T = kv.shape[1]
+    return (q.new_empty(B, L, T, dtype=F32), q.new_empty(B, T, L, dtype=F32), q.new_empty(B, L, P, dtype=BF16))
+
+
+@torch.library.custom_op("ste::align_decode", mutates_args=())
+def align_decode(emit: Tensor, ntok: Tensor, nfrm: Tensor) -> tuple[Tensor, Tensor]:
+    """Monotone (Viterbi) path through emit fp32 [B, T, L] (frame-major log alignment) for ntok[b]
+    tokens over nfrm[b] frames -> (spans int32 [B, L, 2] = (first frame, last frame + 1), -1 past a
+    pair's tokens; score fp32 [B]).  Forward only."""
+    return ops.align_decode(emit.float().contiguous(), ntok.to(torch.int32).contiguous(),
+                            nfrm.to(torch.int32).contiguous())
+
+
+@align_decode.register_fake
+def _align_decode_fake(emit, ntok, nfrm):
+    B, _, L = emit.shape
+    return emit.new_empty(B, L, 2, dtype=torch.int32), emit.new_empty(B, dtype=F32)
+
+
+OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim", "xattn_mq",
+       "align_matrix", "align_decode")
