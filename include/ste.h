@@ -457,12 +457,29 @@ int ste_xattn_bwd(const float* q, const void* k, const void* v, int64_t ldkv, co
  * ste_xattn_gather_fwd: pair r attends with row qrow[r] of q (fp32 [*,P]) over block kvblk[r] of k / v /
  *   mask (rows kvblk[r]*S + s); out fp32 [R,P]; a negative qrow[r] or kvblk[r] writes a zero row.
  *   S <= 16384 and fewer than 2^31 rows of k / v in all.  The arithmetic of ste_xattn1_fwd at drop_p = 0: bitwise equal to it on replicated
- *   inputs. */
+ *   inputs.
+ * ste_xattn_seg_fwd: R (query, segment) pairs; a segment is a run of rows anywhere in one k / v buffer (a
+ *   store of corpus clips' valid frames).  Pair r attends with row qrow[r] of q (fp32 [U,P]) over rows
+ *   seg_row[g] .. seg_row[g] + seg_len[g] - 1 of k / v, g = pseg[r]; seg_row int64 [G] (every row address
+ *   is 64-bit), seg_len int32 [G], S = seg_len[g] unbounded; no mask operand (only valid rows are stored).
+ *   out fp32 [R,P]; a pair with qrow[r] < 0, pseg[r] < 0 or seg_len[g] == 0 gets a zero row.  The pairs
+ *   come SORTED BY SEGMENT: pseg is non-decreasing with its -1 entries last, and the tile table
+ *   tile_first / tile_cnt int32 [ntile] cuts them into tiles of at most 16 consecutive pairs of ONE
+ *   segment (pairs tile_first[t] .. tile_first[t] + tile_cnt[t] - 1; a tile with count 0 reads no key;
+ *   the -1 pairs belong to no tile).  A block owns (tile, head), so a segment's head slice is read once
+ *   per 16 of its queries.  Per pair the arithmetic is ste_xattn_mq_fwd's, instruction for instruction
+ *   (same bound, same bits as that kernel on the same rows without a mask): a pair's out row depends on
+ *   its query row and its segment's rows alone, not on R, G, its position, its tile-mates or where the
+ *   segment lies.  R, G, ntile >= 1, else STE_ERR_SHAPE. */
 int ste_xattn_mq_fwd(const float* q, const int32_t* qrow, const void* k, const void* v, int64_t ldkv,
                      const int32_t* mask, int B, int C, int S, int P, int nh, float scale, float* out, void* stream);
 int ste_xattn_gather_fwd(const float* q, const int32_t* qrow, const void* k, const void* v, int64_t ldkv,
                          const int32_t* kvblk, const int32_t* mask, int R, int S, int P, int nh, float scale,
                          float* out, void* stream);
+int ste_xattn_seg_fwd(const float* q, const int32_t* qrow, const int32_t* pseg, const void* k, const void* v,
+                      int64_t ldkv, const int64_t* seg_row, const int32_t* seg_len, const int32_t* tile_first,
+                      const int32_t* tile_cnt, int ntile, int R, int G, int P, int nh, float scale, float* out,
+                      void* stream);
 /* As ste_xattn_bwd, but dk/dv are bf16 and WRITTEN (not accumulated), and colsum_part fp32
  * [B, 2P] receives per-sample column sums of dk (cols [0,P)) and dv (cols [P,2P)) in fp32, for the
  * key/value bias gradient; lddkv % 8 == 0. */

@@ -193,6 +193,9 @@ _SIGS = {
                                  c_int, c_int, c_float, c_void_p, c_void_p]),
     "ste_xattn_gather_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int,
                                      c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    "ste_xattn_seg_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p,
+                                  c_void_p]),
     "ste_align_attn_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                    c_float, c_uint64, c_void_p, c_void_p, c_int64, c_void_p]),
     "ste_align_attn_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_int,

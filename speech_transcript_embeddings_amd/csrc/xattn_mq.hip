@@ -2,7 +2,10 @@
 //   ste_xattn_mq_fwd      C single-vector queries per clip against that clip's K/V (text -> audio):
 //                         online softmax over key tiles, Q·Kᵀ and P·V on the bf16 MFMA;
 //   ste_xattn_gather_fwd  one query per pair against a K/V block chosen per pair (audio -> text):
-//                         xattn_fwd_kernel<1> of xattn_fwd.h with gathered addresses.
+//                         xattn_fwd_kernel<1> of xattn_fwd.h with gathered addresses;
+//   ste_xattn_seg_fwd     (query, segment) pairs against runs of rows of one K/V buffer (a text query
+//                         against stored corpus clips): the body of ste_xattn_mq_fwd on tiles of
+//                         pairs that share a segment.
 #include "common.h"
 #include "xattn_fwd.h"
 #include "../../include/ste.h"
@@ -22,7 +25,8 @@ STE_DEV float xrow_max(float v) {
   return fmaxf(__builtin_bit_cast(float, (uint32_t)q[0]), __builtin_bit_cast(float, (uint32_t)q[1]));
 }
 
-// One block per (clip b, head hh, tile of 16 query slots).  All MFMAs are 16x16x32 bf16 with the
+// The work of one block, shared by the two kernels below: up to 16 query slots against one head slice
+// of one run of S key/value rows.  All MFMAs are 16x16x32 bf16 with the
 // query on the B side, so a lane's column (lane & 15 = li) is its query slot throughout and the
 // softmax state (m, l) of a query lives in the four lanes li, li+16, li+32, li+48:
 //   Sᵀ   = K·Qᵀ      A = K rows (key li of a 16-key half, d = 32·ds + 8g + j), B = Q (hi, then lo)
@@ -33,11 +37,12 @@ STE_DEV float xrow_max(float v) {
 // Wave w takes key tiles w, w + 4, ... (a function of S alone) and wave 0 folds the waves' (m, l, acc)
 // in the order 0, 1, 2, 3, so a slot's result does not depend on C, B, its position or its neighbours.
 // DHMAX: head dim rounded up to 32, 64, 128 or 256 (register arrays are sized by it).
+// row: the lane's row of q (-1 = empty slot); k / v: row 0 of the run; mask: the run's key mask or
+// NULL; o: the lane's out row (NULL = no slot), columns from c0 on.  S >= 1.
 template <int DHMAX>
-__global__ __launch_bounds__(NT) void xattn_mq_kernel(const float* __restrict__ q, const int32_t* __restrict__ qrow,
-                                                    const bf16* __restrict__ k, const bf16* __restrict__ v,
-                                                    int64_t ldkv, const int32_t* __restrict__ mask, int C, int S,
-                                                    int P, int nh, int QT, float scale, float* __restrict__ out) {
+STE_DEV void xattn_mq_tile(const float* __restrict__ q, int row, const bf16* __restrict__ k,
+                           const bf16* __restrict__ v, int64_t ldkv, const int32_t* __restrict__ mask, int S, int P,
+                           int dh, int c0, float scale, float* __restrict__ o) {
   constexpr int NDS = DHMAX / 32;                 // d steps of Q·Kᵀ
   constexpr int NCT = DHMAX / 16;                 // 16-column tiles of out
   constexpr int VC = DHMAX < 128 ? DHMAX : 128;   // V columns staged at a time
@@ -48,10 +53,7 @@ __global__ __launch_bounds__(NT) void xattn_mq_kernel(const float* __restrict__ 
   __shared__ __attribute__((aligned(16))) char smem[LDSB];
   __shared__ float sml[3][2][64];
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, li = lane & 15, g = lane >> 4;
-  const int bid = blockIdx.x, qt = bid % QT, hh = (bid / QT) % nh, b = bid / (QT * nh);
-  const int dh = P / nh, c0 = hh * dh, dh16 = (dh + 15) & ~15;
-  const int c = qt * 16 + li;  // this lane's query slot
-  const int row = c < C ? qrow[(int64_t)b * C + c] : -1;
+  const int dh16 = (dh + 15) & ~15;
 
   // the query as bf16 hi + lo (zero for an empty slot and past dh)
   bf16x8 qh[NDS], ql[NDS];
@@ -83,7 +85,7 @@ __global__ __launch_bounds__(NT) void xattn_mq_kernel(const float* __restrict__ 
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
       const int key = min(s0 + 16 * hf + li, S - 1);  // rows past S are masked below
-      const bf16* kr = k + ((int64_t)b * S + key) * ldkv + c0;
+      const bf16* kr = k + (int64_t)key * ldkv + c0;
       f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ds = 0; ds < NDS; ++ds) {
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(NT) void xattn_mq_kernel(const float* __restrict__ 
         const int kk = s0 + 16 * hf + 4 * g + r;
         float x = a[r] * scale;
         if (kk >= S) x = -INFINITY;
-        else if (mask && mask[(int64_t)b * S + kk] == 0) x = -1e9f;
+        else if (mask && mask[kk] == 0) x = -1e9f;
         sc[hf][r] = x;
       }
     }
@@ -133,7 +135,7 @@ __global__ __launch_bounds__(NT) void xattn_mq_kernel(const float* __restrict__ 
           const int col = cb + 8 * cc;
           bf16x8 x = zero8;
           if (s0 + kr < S && col < dh)
-            x = *reinterpret_cast<const bf16x8*>(v + ((int64_t)b * S + s0 + kr) * ldkv + c0 + col);
+            x = *reinterpret_cast<const bf16x8*>(v + (int64_t)(s0 + kr) * ldkv + c0 + col);
           *reinterpret_cast<bf16x8*>(vt + (kr * VLD + 8 * cc) * 2) = x;
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -176,8 +178,7 @@ __global__ __launch_bounds__(NT) void xattn_mq_kernel(const float* __restrict__ 
     m = mn;
   }
   const float inv = 1.f / xrow32_sum(l);
-  if (c < C) {
-    float* o = out + ((int64_t)b * C + c) * P + c0;
+  if (o) {
 #pragma unroll
     for (int ct = 0; ct < NCT; ++ct) {
       const int col = 16 * ct + 4 * g;
@@ -185,6 +186,50 @@ __global__ __launch_bounds__(NT) void xattn_mq_kernel(const float* __restrict__ 
         *reinterpret_cast<f32x4*>(o + col) = row >= 0 ? acc[ct] * inv : f32x4{0.f, 0.f, 0.f, 0.f};
     }
   }
+}
+
+// ste_xattn_mq_fwd: one block per (clip b, head hh, tile of 16 query slots of the clip's C)
+template <int DHMAX>
+__global__ __launch_bounds__(NT) void xattn_mq_kernel(const float* __restrict__ q, const int32_t* __restrict__ qrow,
+                                                    const bf16* __restrict__ k, const bf16* __restrict__ v,
+                                                    int64_t ldkv, const int32_t* __restrict__ mask, int C, int S,
+                                                    int P, int nh, int QT, float scale, float* __restrict__ out) {
+  const int bid = blockIdx.x, qt = bid % QT, hh = (bid / QT) % nh, b = bid / (QT * nh);
+  const int dh = P / nh, c0 = hh * dh;
+  const int c = qt * 16 + (threadIdx.x & 15);  // this lane's query slot
+  const int row = c < C ? qrow[(int64_t)b * C + c] : -1;
+  xattn_mq_tile<DHMAX>(q, row, k + (int64_t)b * S * ldkv, v + (int64_t)b * S * ldkv, ldkv,
+                       mask ? mask + (int64_t)b * S : nullptr, S, P, dh, c0, scale,
+                       c < C ? out + ((int64_t)b * C + c) * P + c0 : nullptr);
+}
+
+// ste_xattn_seg_fwd: one block per (tile, head hh).  Tile t is the cnt <= 16 consecutive pairs from
+// tile_first[t] on, all of segment pseg[tile_first[t]]: rows seg_row[g] .. seg_row[g] + seg_len[g] - 1
+// of k / v.  An empty tile (count 0) or a tile of an empty or negative segment returns before it
+// reads a key: its out rows keep the zeros the host wrote.
+template <int DHMAX>
+__global__ __launch_bounds__(NT) void xattn_seg_kernel(const float* __restrict__ q, const int32_t* __restrict__ qrow,
+                                                     const int32_t* __restrict__ pseg, const bf16* __restrict__ k,
+                                                     const bf16* __restrict__ v, int64_t ldkv,
+                                                     const int64_t* __restrict__ seg_row,
+                                                     const int32_t* __restrict__ seg_len,
+                                                     const int32_t* __restrict__ tile_first,
+                                                     const int32_t* __restrict__ tile_cnt, int R, int G, int P, int nh,
+                                                     float scale, float* __restrict__ out) {
+  const int t = blockIdx.x / nh, hh = blockIdx.x % nh;
+  const int first = tile_first[t], cnt = min(tile_cnt[t], 16);
+  if (cnt <= 0 || first < 0 || first > R - cnt) return;
+  const int g = pseg[first];
+  if (g < 0 || g >= G) return;
+  const int S = seg_len[g];
+  if (S <= 0) return;
+  const int dh = P / nh, c0 = hh * dh;
+  const int c = threadIdx.x & 15;
+  const int r = first + c;
+  const int row = c < cnt ? qrow[r] : -1;
+  const int64_t base = seg_row[g] * ldkv;
+  xattn_mq_tile<DHMAX>(q, row, k + base, v + base, ldkv, nullptr, S, P, dh, c0, scale,
+                       c < cnt ? out + (int64_t)r * P + c0 : nullptr);
 }
 
 // the rule of ste_xattn_fwd (heads.hip), without its cap on S
@@ -226,6 +271,32 @@ extern "C" int ste_xattn_gather_fwd(const float* q, const int32_t* qrow, const v
   hipLaunchKernelGGL((xattn_fwd_kernel<1, true>), dim3(R, nh), dim3(NT), (size_t)S * sizeof(float),
                      (hipStream_t)stream, q, (const bf16*)k, (const bf16*)v, ldkv, mask, R, S, P, nh, scale, 0.f,
                      (uint64_t)0, (uint64_t)0, (float*)nullptr, out, qrow, kvblk);
+  STE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ste_xattn_seg_fwd(const float* q, const int32_t* qrow, const int32_t* pseg, const void* k,
+                                 const void* v, int64_t ldkv, const int64_t* seg_row, const int32_t* seg_len,
+                                 const int32_t* tile_first, const int32_t* tile_cnt, int NTILE, int R, int G, int P,
+                                 int nh, float scale, float* out, void* stream) {
+  if (R <= 0 || G <= 0 || NTILE <= 0 || !xattn_dims_ok(P, nh) || (ldkv & 7) || ldkv < P ||
+      (((uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15))
+    return STE_ERR_SHAPE;
+  const int dh = P / nh;
+  const int64_t blocks = (int64_t)NTILE * nh;
+  if (blocks > 0x7fffffff) return STE_ERR_SHAPE;
+  // rows of pairs that no tile covers (an empty pair, an empty segment) are zeros
+  hipError_t e = hipMemsetAsync(out, 0, (size_t)R * P * sizeof(float), (hipStream_t)stream);
+  if (e != hipSuccess) return (int)e;
+#define STE_SEG_LAUNCH(D)                                                                                      \
+  hipLaunchKernelGGL(xattn_seg_kernel<D>, dim3((unsigned)blocks), dim3(NT), 0, (hipStream_t)stream, q, qrow, \
+                     pseg, (const bf16*)k, (const bf16*)v, ldkv, seg_row, seg_len, tile_first, tile_cnt, R, G, P, \
+                     nh, scale, out)
+  if (dh <= 32) STE_SEG_LAUNCH(32);
+  else if (dh <= 64) STE_SEG_LAUNCH(64);
+  else if (dh <= 128) STE_SEG_LAUNCH(128);
+  else STE_SEG_LAUNCH(256);
+#undef STE_SEG_LAUNCH
   STE_CHECK_LAUNCH();
   return 0;
 }

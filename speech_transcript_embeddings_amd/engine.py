@@ -1264,6 +1264,76 @@ class Engine:
         ops.topk_target_score(unit(afused), unit(tfused), live, scores)
         return scores.view(B, C)
 
+    @torch.no_grad()
+    def score_clips(self, tproj, th, tmask, store, candidates):
+        """score_pairs in the other direction: the fused pair score of k candidate corpus
+        clips per text query.  text [Q,P] + hidden [Q,L,Ht] + mask [Q,L]; store: a
+        retrieval.AudioStateStore built with these weights (else RuntimeError); candidates int [Q,k]
+        of clip ids in [-1, len(store)) -> scores fp32 [Q,k], -inf for an empty (-1) slot.
+
+        The pair form of score_pairs: the text K/V is projected once per query and the audio query
+        once per DISTINCT candidate clip; the pairs are grouped by clip (retrieval.plan_clip_pairs),
+        pair (i, n)'s text query attends over clip n's stored K/V rows in place (xattn_seg_fwd) and
+        clip n's audio query over text i (xattn_gather_fwd); then score_pairs' chain.  Without
+        use_cross_modal the score is the cosine of the stored unit row."""
+        from .retrieval import plan_clip_pairs
+        m, dev, s = self.m, self.s.device, self.s
+        Q, L, Ht = th.shape
+        P = m.projection_dim
+        cand = candidates.to(dev, torch.int32).contiguous()
+        if cand.dim() != 2 or cand.shape[0] != Q or cand.shape[1] < 1:
+            raise ValueError(f"candidates must be [{Q}, k >= 1], got {tuple(cand.shape)}")
+        lo, hi = (int(x) for x in torch.stack((cand.min(), cand.max())).tolist())
+        if lo < -1 or hi >= len(store):
+            raise ValueError(f"candidates must lie in [-1, {len(store)}), got [{lo}, {hi}]")
+        store.check()
+        k = cand.shape[1]
+        R = Q * k
+        tproj = tproj.float().contiguous()
+
+        def unit(x):
+            y = self._e(*x.shape)
+            ops.l2norm_fwd(x, y, self._e(x.shape[0]))
+            return y
+
+        if not m.use_cross_modal:
+            scores = torch.full((R,), float("-inf"), device=dev, dtype=F32)
+            qs = unit(tproj).repeat_interleave(k, 0)
+            for base, rows in store.index.chunks:
+                ops.topk_target_score(qs, rows, cand.view(-1), scores, index_base=base)
+            return scores.view(Q, k)
+        if hi < 0:
+            return torch.full((Q, k), float("-inf"), device=dev, dtype=F32)
+        nh = m.xattn_heads
+        plan = plan_clip_pairs(cand)
+        qrow, pseg = plan["qrow"], plan["pseg"]
+        clips = plan["unique"].long()
+        thb = ops.cast_bf16(th.contiguous(), self._e(Q * L, Ht, dtype=BF16))
+        tm32 = self._mask32(tmask, Q * L) if tmask is not None else None
+        kvt, _ = self._kv("audio_to_text_attention", "text_seq_to_projection", thb)     # once per query
+        aproj = store.aproj.index_select(0, clips)                                      # the distinct clips
+        qt = ops.linear(tproj, self._w32("text_to_audio_attention.query.weight"),
+                        s.p("text_to_audio_attention.query.bias"))
+        qa = ops.linear(aproj, self._w32("audio_to_text_attention.query.weight"),
+                        s.p("audio_to_text_attention.query.bias"))
+        live = torch.where(pseg < 0, pseg, torch.arange(R, device=dev, dtype=torch.int32))
+        tcat, acat = self._e(R, 2 * P), self._e(R, 2 * P)
+        att = self._e(R, P)
+        ops.xattn_seg_fwd(qt, qrow, pseg, store.kv[:, :P], store.kv[:, P:], store.seg_row.index_select(0, clips),
+                          store.frames.index_select(0, clips), plan["tile_first"], plan["tile_cnt"], nh, att)
+        ops.linear(att, self._w32("text_to_audio_attention.out_proj.weight"),
+                   s.p("text_to_audio_attention.out_proj.bias"), out=tcat[:, P:])
+        ops.copy2d(tcat[:, :P], tproj.index_select(0, qrow.clamp(min=0).long()))
+        ops.xattn_gather_fwd(qa, pseg, kvt[:, :P], kvt[:, P:], qrow, tm32, R, L, nh, att)
+        ops.linear(att, self._w32("audio_to_text_attention.out_proj.weight"),
+                   s.p("audio_to_text_attention.out_proj.bias"), out=acat[:, P:])
+        ops.copy2d(acat[:, :P], aproj.index_select(0, pseg.clamp(min=0).long()))
+        tfused, _ = self._fuse_fwd("text_fusion", tcat)
+        afused, _ = self._fuse_fwd("audio_fusion", acat)
+        scores = torch.full((R,), float("-inf"), device=dev, dtype=F32)
+        ops.topk_target_score(unit(afused), unit(tfused), live, scores)
+        return scores.index_select(0, plan["inverse"].view(-1)).view(Q, k)
+
     def cross_backward(self, sv, d_tf, d_af):
         """-> (d text_projected [b,P], d text_hidden [b*L,Ht], d audio_projected [b,P],
         d audio_hidden [b*T,Ha]) fp32; parameter gradients += into the flat gradient buffer."""

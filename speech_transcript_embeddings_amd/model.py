@@ -305,6 +305,25 @@ class EnhancedAudioTextModel(nn.Module):
                                        audio_context)
 
     @torch.no_grad()
+    def score_clips(self, input_ids, attention_mask, store, candidates, *, text_encoded=None):
+        """score_candidates in the other direction: the fused pair score of k candidate corpus clips
+        per text query -> fp32 [Q, k], -inf for an empty slot.  store: a retrieval.AudioStateStore
+        built from this model with its present weights; candidates int [Q, k] are clip ids of the
+        store (-1 = empty), as returned by store.search.  One text-encoder pass per query and no audio
+        pass: the clips' states are read from the store (Engine.score_clips).  text_encoded: the
+        (projection, hidden) pair of an encode_text call already made on these transcripts in eval
+        mode, to skip the text pass.  Forward only, inference arithmetic."""
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        was_training, self.training = self.training, False   # encode_text reads the flag: no dropout here
+        try:
+            tproj, th = text_encoded or self.encode_text(input_ids, attention_mask)
+        finally:
+            self.training = was_training
+        self.store.sync_shadow()
+        return self.engine.score_clips(tproj, th, attention_mask, store, candidates)
+
+    @torch.no_grad()
     def align(self, input_values, attention_mask_audio, input_ids, attention_mask=None, *, word_ids=None,
               audio_encoded=None, text_encoded=None, return_matrix=False):
         """Where in clip b is each token of transcript b, and how confident is the alignment head

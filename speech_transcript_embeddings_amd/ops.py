@@ -690,6 +690,24 @@ def xattn_gather_fwd(q, qrow, k, v, kvblk, mask, R, S, nh, out):
          float((P // nh) ** -0.5), ptr(out), _s())
 
 
+def xattn_seg_fwd(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, nh, out):
+    """Pair r attends with row qrow[r] of q [U, P] over the segment pseg[r]: rows seg_row[g] ..
+    seg_row[g] + seg_len[g] - 1 of k / v (bf16, one buffer).  Pairs sorted by segment, -1 last, cut
+    into tiles of <= 16 pairs of one segment by tile_first / tile_cnt (retrieval.plan_clip_pairs).
+    out fp32 [R, P]; an empty pair or segment gives a zero row.  The arithmetic of xattn_mq_fwd."""
+    P = q.shape[-1]
+    R, G = qrow.numel(), seg_row.numel()
+    assert q.dtype == F32 and q.is_contiguous() and out.dtype == F32 and out.shape == (R, P) and out.is_contiguous()
+    assert qrow.dtype == torch.int32 and pseg.dtype == torch.int32 and pseg.numel() == R
+    assert seg_row.dtype == torch.int64 and seg_len.dtype == torch.int32 and seg_len.numel() == G
+    assert tile_first.dtype == torch.int32 and tile_cnt.dtype == torch.int32
+    assert tile_first.numel() == tile_cnt.numel()
+    assert all(t.is_contiguous() for t in (qrow, pseg, seg_row, seg_len, tile_first, tile_cnt))
+    assert k.dtype == BF16 and v.dtype == BF16 and _ld(k) == _ld(v)
+    call("ste_xattn_seg_fwd", ptr(q), ptr(qrow), ptr(pseg), ptr(k), ptr(v), _ld(k), ptr(seg_row), ptr(seg_len),
+         ptr(tile_first), ptr(tile_cnt), tile_first.numel(), R, G, P, nh, float((P // nh) ** -0.5), ptr(out), _s())
+
+
 def xattn_bwd(q, k, v, probs, dout, B, S, nh, dq, dk, dv, seeds, drop_p=0.0, colsum=None, mask=None):
     """dk/dv fp32: accumulated (+=).  dk/dv bf16: written (ste_xattn_bwd_bf16), and the fp32
     column sums of [dk | dv] are added into colsum [2P] when given."""

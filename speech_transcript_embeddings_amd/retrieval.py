@@ -21,6 +21,14 @@ trained on (model.score_candidates: one audio pass per clip, one text pass per d
     rerank(model, input_values, attention_mask_audio, text_ids, text_mask, idx) -> (values, indices)
     evaluate_retrieval(..., rerank_k=k)           -> also "a2t_rerank"
 
+The other direction, a typed phrase against the corpus of clips, needs the audio states
+of every clip; they are computed once when the corpus is indexed and attended over in place:
+
+    AudioStateStore(model): add(input_values, mask), len(), frames, nbytes, search(text_emb, k)
+    plan_clip_pairs(idx)                          -> the (query, clip) pairs grouped by clip, in tiles
+    rerank_clips(model, input_ids, attention_mask, store, idx) -> (values, indices)
+    evaluate_retrieval(..., rerank_k=k, rerank_t2a=True) -> also "t2a_rerank"
+
 Scores and selection run in ste_topk_sim (csrc/retrieval.hip): the queries x corpus score matrix
 is never written.  The order is total (value descending, index ascending) and a row's score is
 bit-identical wherever it is computed, so results do not depend on how the corpus was chunked.
@@ -189,6 +197,186 @@ def rerank(model, input_values, attention_mask_audio, text_ids, text_mask, idx, 
     return rerank_order(scores, idx.to(scores.device))
 
 
+# ------------------------------------------------- stage 2, text -> clips
+def plan_clip_pairs(idx: torch.Tensor) -> dict:
+    """Candidate lists idx [Q, k] of clip ids (-1 = empty) -> the (query, clip) pairs grouped for
+    ste_xattn_seg_fwd.  The R = Q·k pairs are sorted by clip with a stable sort, so pairs of one clip
+    keep their (query, column) order and the empty ones come last; the distinct clips become the
+    segments through plan_candidates.  Returns a dict of
+        unique      [G] the distinct clip ids, ascending (dtype of idx)
+        order       int64 [R]: sorted pair j is flat slot order[j] = query·k + column
+        inverse     int64 [Q, k]: slot (q, c) is sorted pair inverse[q, c] (sorted[inverse] restores [Q, k])
+        qrow        int32 [R]: the query of sorted pair j, -1 for an empty pair
+        pseg        int32 [R]: its segment (index into unique), non-decreasing, -1 for an empty pair
+        tile_first, tile_cnt  int32 [tiles]: tile t holds the sorted pairs tile_first[t] ..
+                    tile_first[t] + tile_cnt[t] - 1, all of one segment and at most 16; a clip
+                    retrieved by c queries gets ceil(c / 16) tiles and the empty pairs get none.
+    Pure torch, any device."""
+    idx = torch.as_tensor(idx)
+    if idx.dim() != 2:
+        raise ValueError(f"candidate lists must be [Q, k], got {tuple(idx.shape)}")
+    k = max(int(idx.shape[1]), 1)
+    dev = idx.device
+    unique, slots = plan_candidates(idx)
+    G = unique.numel()
+    flat = slots.reshape(-1).to(torch.int64)
+    order = torch.sort(torch.where(flat >= 0, flat, torch.full_like(flat, G)), stable=True)[1]
+    pseg = flat[order]
+    R = order.numel()
+    inverse = torch.empty_like(order)
+    inverse[order] = torch.arange(R, device=dev)
+    qrow = torch.where(pseg >= 0, order // k, torch.full_like(order, -1))
+    counts = torch.bincount(flat[flat >= 0], minlength=G)            # pairs per segment
+    ntile = (counts + 15) // 16
+    seg = torch.repeat_interleave(torch.arange(G, device=dev), ntile)                 # segment of each tile
+    within = torch.arange(seg.numel(), device=dev) - (torch.cumsum(ntile, 0) - ntile)[seg]
+    tile_first = (torch.cumsum(counts, 0) - counts)[seg] + 16 * within
+    tile_cnt = torch.clamp(counts[seg] - 16 * within, max=16)
+    return dict(unique=unique, order=order, inverse=inverse.view(idx.shape), qrow=qrow.to(I32), pseg=pseg.to(I32),
+                tile_first=tile_first.to(I32), tile_cnt=tile_cnt.to(I32))
+
+
+class AudioStateStore:
+    """What the text -> audio fused pair score needs of every corpus clip, computed once when the
+    corpus is indexed: the clip's projection aproj fp32 [P], its unit row (in an
+    EmbeddingIndex, for stage 1) and the bf16 text_to_audio_attention K|V rows [frames, 2P] of its
+    VALID frames, appended to one growable buffer [capacity, 2P] (geometric growth; reserve_frames
+    preallocates) that ste_xattn_seg_fwd attends over in place.  Clip n is the segment of rows
+    seg_row[n] .. seg_row[n] + frames[n] - 1.  Dropping the padded frames is exact (§18), so the
+    audio mask must be a prefix mask with at least one valid frame, else ValueError.  3 KB per frame
+    at P = 768: 1.5 MB per 10 s clip.  Without use_cross_modal only aproj and the unit rows are kept.
+
+    The store is valid for the weights it was built with: it records the model's
+    ParamStore.weights_token() at the first add, and adding to or scoring against it after the
+    weights changed raises RuntimeError (check)."""
+
+    def __init__(self, model, device="cuda", index_dtype: torch.dtype = F32, reserve_frames: int = 0):
+        self.model, self.device = model, torch.device(device)
+        self.dim = int(model.projection_dim)
+        self.fused = bool(getattr(model, "use_cross_modal", False))
+        self.index = EmbeddingIndex(self.dim, index_dtype, self.device)
+        self.kv = torch.empty(max(int(reserve_frames), 0) if self.fused else 0, 2 * self.dim, device=self.device,
+                              dtype=BF16)
+        self.rows = 0                         # rows of kv in use
+        self._seg_row: list[int] = []
+        self._seg_len: list[int] = []
+        self._aproj: list[torch.Tensor] = []
+        self._dev = None                      # (seg_row int64 [N], frames int32 [N], aproj [N, P]) on the device
+        self._token = None
+
+    def __len__(self) -> int:
+        return len(self._seg_len)
+
+    def check(self) -> None:
+        """Raise if the model's weights changed since the store was built."""
+        if self._token is not None and self._token != self.model.store.weights_token():
+            raise RuntimeError("the AudioStateStore was built with other weights: rebuild it after a weight update")
+
+    def _reserve(self, rows: int) -> None:
+        if rows <= self.kv.shape[0]:
+            return
+        grown = torch.empty(max(rows, 2 * self.kv.shape[0]), self.kv.shape[1], device=self.device, dtype=BF16)
+        grown[:self.rows].copy_(self.kv[:self.rows])
+        self.kv = grown
+
+    @torch.no_grad()
+    def add(self, input_values, attention_mask_audio=None, *, audio_encoded=None) -> None:
+        """Append a batch of clips: one model.encode_audio pass in eval arithmetic (or its result
+        audio_encoded = (projection, hidden)), one K/V projection, one device -> host sync (the
+        frame counts and the mask check)."""
+        model, eng = self.model, self.model.engine
+        self.check()
+        if audio_encoded is None:
+            was_training, model.training = model.training, False   # encode_audio reads the flag: no dropout here
+            try:
+                audio_encoded = model.encode_audio(input_values, attention_mask_audio)
+            finally:
+                model.training = was_training
+        aproj, ah = audio_encoded
+        B, T, Ha = ah.shape
+        am = attention_mask_audio
+        if am is not None and eng.raw_audio and am.shape[-1] != T:
+            from .wav2vec2 import frame_mask   # a sample-level wav2vec2 mask, as in score_pairs
+            am32 = frame_mask(eng.acfg, am, B, am.shape[-1], T, self.device)[1]
+        else:
+            am32 = eng._mask32(am.to(self.device, torch.int64), B * T) if am is not None else None
+        if am32 is None:
+            frames = [T] * B
+        else:
+            fm = am32.view(B, T) != 0
+            bad = (fm[:, 1:] & ~fm[:, :-1]).any() | (~fm.any(1)).any()
+            *frames, bad = torch.cat([fm.sum(1), bad.view(1).to(torch.int64)]).tolist()
+            if bad:
+                raise ValueError("AudioStateStore.add needs prefix audio masks with at least one valid frame per clip")
+        if self.fused:
+            model.store.sync_shadow()
+            ahb = ops.cast_bf16(ah.reshape(B * T, Ha).float().contiguous(),
+                                torch.empty(B * T, Ha, device=self.device, dtype=BF16))
+            kv = eng._kv("text_to_audio_attention", "audio_seq_to_projection", ahb)[0]
+            self._reserve(self.rows + sum(frames))
+            if all(n == T for n in frames):
+                self.kv[self.rows:self.rows + B * T].copy_(kv)
+            else:
+                at = self.rows
+                for b, n in enumerate(frames):
+                    self.kv[at:at + n].copy_(kv[b * T:b * T + n])
+                    at += n
+        for n in frames:
+            self._seg_row.append(self.rows)
+            self._seg_len.append(n)
+            self.rows += n
+        aproj = aproj.detach().float()
+        self._aproj.append(aproj.clone())
+        self.index.add(_unit_rows(aproj))
+        self._dev = None
+        if self._token is None:
+            self._token = model.store.weights_token()
+
+    def _tables(self):
+        if self._dev is None:
+            self._dev = (torch.tensor(self._seg_row, dtype=torch.int64, device=self.device),
+                         torch.tensor(self._seg_len, dtype=I32, device=self.device),
+                         torch.cat(self._aproj) if self._aproj else torch.empty(0, self.dim, device=self.device))
+            self._aproj = [self._dev[2]] if self._aproj else []
+        return self._dev
+
+    @property
+    def seg_row(self) -> torch.Tensor:
+        """int64 [N]: the first row of each clip's K/V in kv."""
+        return self._tables()[0]
+
+    @property
+    def frames(self) -> torch.Tensor:
+        """int32 [N]: the valid frames (stored K/V rows) of each clip."""
+        return self._tables()[1]
+
+    @property
+    def aproj(self) -> torch.Tensor:
+        """fp32 [N, P]: the clips' projections."""
+        return self._tables()[2]
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes held for the clips added so far (the K/V rows in use, aproj, the unit rows and the segment table)."""
+        n = len(self)
+        return (self.rows * self.kv.shape[1] * 2 + n * self.dim * 4
+                + n * self.dim * (2 if self.index.dtype == BF16 else 4) + n * 12)
+
+    def search(self, text_emb: torch.Tensor, k: int):
+        """Stage 1: (values fp32 [Q, k], indices int32 [Q, k]) of the k best clips per unit text row,
+        as EmbeddingIndex.search."""
+        return self.index.search(text_emb, k)
+
+
+@torch.no_grad()
+def rerank_clips(model, input_ids, attention_mask, store, idx, *, text_encoded=None):
+    """Rerank each text query's retrieved clips idx [Q, k] (clip ids of an AudioStateStore, as
+    returned by store.search) with the fused pair score: model.score_clips -> rerank_order.
+    Returns (values fp32 [Q, k], indices [Q, k]).  text_encoded: see score_clips."""
+    scores = model.score_clips(input_ids, attention_mask, store, idx, text_encoded=text_encoded)
+    return rerank_order(scores, torch.as_tensor(idx).to(scores.device))
+
+
 def _pad_rows(chunks, fill):
     """Concatenate [n_i, L_i] chunks, right-padded to the longest L with fill."""
     L = max(c.shape[1] for c in chunks)
@@ -197,7 +385,7 @@ def _pad_rows(chunks, fill):
 
 @torch.no_grad()
 def evaluate_retrieval(model, data_loader, device, ks=(1, 5, 10), index_dtype: torch.dtype = F32,
-                       return_ranks: bool = False, rerank_k: int = 0) -> dict:
+                       return_ranks: bool = False, rerank_k: int = 0, rerank_t2a: bool = False) -> dict:
     """One pass over a loader of the reference's batch dicts (custom_collate_fn's keys): embeds the
     clean transcripts and the audio, indexes both and ranks pair i's partner for query i in both
     directions.  Returns {"a2t": retrieval_metrics, "t2a": retrieval_metrics} (audio -> text,
@@ -213,10 +401,17 @@ def evaluate_retrieval(model, data_loader, device, ks=(1, 5, 10), index_dtype: t
     becomes its position in that list when it is among them.  The second pass must yield the same
     items in the same order (a loader with shuffle=False over a deterministic dataset); each
     batch's input_ids_pos is compared with the stored rows and a mismatch raises ValueError.
-    Out of scope: reranking text -> audio (it needs the audio states of arbitrary corpus clips),
-    the model_infer.py variant, a cache of the corpus text K/V, and any backward."""
+
+    rerank_t2a=True (with rerank_k > 0 and a use_cross_modal model) adds "t2a_rerank" (and
+    "t2a_rerank_ranks"), the other direction: the first pass also fills an AudioStateStore with the
+    clips' audio states, and after it each batch of clean transcripts (the kept token rows) is
+    reranked against store.search(text_emb, rerank_k) with rerank_clips.  This direction needs no
+    further loader pass.  With the flag off nothing changes.
+    Out of scope: the model_infer.py variant, a cache of the corpus text K/V, and any backward."""
     model.eval()
     do_rerank = rerank_k > 0 and getattr(model, "use_cross_modal", False)
+    do_t2a = do_rerank and rerank_t2a
+    store = None
     texts, audios, tok_ids, tok_mask = [], [], [], []
     text_index = audio_index = None
 
@@ -228,12 +423,20 @@ def evaluate_retrieval(model, data_loader, device, ks=(1, 5, 10), index_dtype: t
             continue
         b = on_device(batch)
         t = embed_texts(model, b["input_ids_pos"], b["attention_mask_pos"])
-        a = embed_audio(model, b["input_values"], b.get("attention_mask_audio"))
+        if do_t2a:
+            enc = model.encode_audio(b["input_values"], b.get("attention_mask_audio"))
+            a = _unit_rows(enc[0])
+            if store is None:
+                store = AudioStateStore(model, a.device, index_dtype)
+            store.add(b["input_values"], b.get("attention_mask_audio"), audio_encoded=enc)   # indexes a as well
+        else:
+            a = embed_audio(model, b["input_values"], b.get("attention_mask_audio"))
         if text_index is None:
             text_index = EmbeddingIndex(t.shape[1], index_dtype, t.device)
-            audio_index = EmbeddingIndex(a.shape[1], index_dtype, a.device)
+            audio_index = store.index if do_t2a else EmbeddingIndex(a.shape[1], index_dtype, a.device)
         text_index.add(t)
-        audio_index.add(a)
+        if not do_t2a:
+            audio_index.add(a)
         texts.append(t)
         audios.append(a)
         if do_rerank:
@@ -254,6 +457,20 @@ def evaluate_retrieval(model, data_loader, device, ks=(1, 5, 10), index_dtype: t
     if text_index is not None:
         ids = _pad_rows(tok_ids, model.text_cfg.pad_token_id)
         mask = _pad_rows(tok_mask, 0)
+    if do_t2a:
+        rr, at = [t2a[:0]], 0
+        for t in texts:                # the first pass's batches of clean transcripts
+            nb = t.shape[0]
+            idx = store.search(t, rerank_k)[1]
+            order = rerank_clips(model, ids[at:at + nb], mask[at:at + nb], store, idx)[1]
+            tgt = torch.arange(at, at + nb, device=idx.device, dtype=idx.dtype)
+            rr.append(reranked_ranks(t2a[at:at + nb], idx, order, tgt))
+            at += nb
+        rr = torch.cat(rr)
+        out["t2a_rerank"] = retrieval_metrics(rr, ks)
+        if return_ranks:
+            out["t2a_rerank_ranks"] = rr
+    if text_index is not None:
         n, at = len(text_index), 0
         for batch in data_loader:
             if batch is None:

@@ -328,6 +328,12 @@ class ParamStore:
                 ops.cast_bf16(src, dst)
                 self._versions[n] = self.params[n]._version
 
+    def weights_token(self):
+        """A value that changes whenever a weight does: the sum of the parameters' _version counters
+        (they only grow; a write outside the optimizer moves one) and opt_epoch (the fused optimizer
+        writes the flat buffers without them).  What an AudioStateStore records to know it is stale."""
+        return sum(p._version for p in self.params.values()), self.opt_epoch
+
     def mark_synced(self):
         """The fused optimizer refreshed the shadow of every trained parameter."""
         for n in self.slots:

@@ -24,6 +24,8 @@ through them); the fused training step itself calls the C ABI directly (engine.p
         the k best corpus rows per query by dot product (retrieval over processor.py:128-146's embeddings)
     ste::xattn_mq(q, qrow, k, v, mask?, C, nh) -> out
         CrossModalAttention core (ref :125-168) for C candidate queries per clip sharing its keys/values
+    ste::xattn_seg(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, nh) -> out
+        the same core for (text query, stored corpus clip) pairs: segments of one K/V buffer
     ste::align_matrix(q, kv, kmask?, nh) -> (matrix, emit, out)
         WordLevelAlignmentModule's head-averaged alignment_matrix (ref :295), its frame-major log, the output
     ste::align_decode(emit, ntok, nfrm) -> (spans, score)
@@ -306,6 +308,29 @@ def _xattn_mq_fake(q, qrow, k, v, mask, C, nh):
     return q.new_empty(qrow.numel(), q.shape[-1], dtype=F32)
 
 
+@torch.library.custom_op("ste::xattn_seg", mutates_args=())
+def xattn_seg(q: Tensor, qrow: Tensor, pseg: Tensor, k: Tensor, v: Tensor, seg_row: Tensor, seg_len: Tensor,
+              tile_first: Tensor, tile_cnt: Tensor, nh: int) -> Tensor:
+    """(query, segment) pairs against runs of rows of one K/V buffer (forward only): q [U, P], qrow /
+    pseg int [R] (sorted by segment, -1 = empty pair -> zero row), k / v [rows, P] (bf16, or fp32 cast
+    to bf16), seg_row int64 [G] / seg_len int [G] (first row and length of a segment), tile_first /
+    tile_cnt int [tiles] (retrieval.plan_clip_pairs) -> out fp32 [R, P]."""
+    out = torch.empty(qrow.numel(), q.shape[-1], device=q.device, dtype=F32)
+
+    def i32(t):
+        return t.reshape(-1).to(torch.int32).contiguous()
+
+    ops.xattn_seg_fwd(q.float().contiguous(), i32(qrow), i32(pseg), _bf16(k), _bf16(v),
+                      seg_row.reshape(-1).to(torch.int64).contiguous(), i32(seg_len), i32(tile_first), i32(tile_cnt),
+                      int(nh), out)
+    return out
+
+
+@xattn_seg.register_fake
+def _xattn_seg_fake(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, nh):
+    return q.new_empty(qrow.numel(), q.shape[-1], dtype=F32)
+
+
 # -------------------------------------------------------------------- alignment
 @torch.library.custom_op("ste::align_matrix", mutates_args=())
 def align_matrix(q: Tensor, kv: Tensor, kmask: Optional[Tensor], nh: int) -> tuple[Tensor, Tensor, Tensor]:
@@ -349,4 +374,4 @@ def _align_decode_fake(emit, ntok, nfrm):
 
 
 OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim", "xattn_mq",
-       "align_matrix", "align_decode")
+       "xattn_seg", "align_matrix", "align_decode")
