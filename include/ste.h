@@ -181,6 +181,12 @@ int ste_gemm_plan_min_tiles(int bf16_tiles, int mx8_tiles, int* prev_bf16, int* 
 /* bf16 x [rows][K] (row stride ldx) -> e4m3 q [rows][K] and E8M0 scales [rows][K/32]:
  * scale 2^e, e = ceil(log2(amax/448)) per 32-element block (no saturation; zero blocks 2^-127). */
 int ste_mx8_quant(const void* x, int64_t ldx, int rows, int K, void* q, void* scales, void* stream);
+/* The inverse reading of those bytes: e4m3 q [rows][K] (row stride ldq bytes) and E8M0 scales
+ * [rows][K/32] -> bf16 out [rows][K], out = bf16(float(e4m3) * 2^(E - 127)) (E = 255 or an e4m3 NaN
+ * byte gives NaN).  e4m3 has 4 significant bits and the scale is a power of two, so the product is
+ * an exact bf16 number unless it falls into bf16's subnormal range (below 2^-126), where it is
+ * rounded to nearest even.  The shape rule of ste_mx8_quant: K % 128 == 0, ldq >= K, ldq % 8 == 0. */
+int ste_mx8_dequant(const void* q, int64_t ldq, int rows, int K, const void* scales, void* out, void* stream);
 
 /* ------------------------------------------------------------- LayerNorm --
  * Replaces nn.LayerNorm forward/backward (every LN of both encoders and the
@@ -470,7 +476,15 @@ int ste_xattn_bwd(const float* q, const void* k, const void* v, int64_t ldkv, co
  *   per 16 of its queries.  Per pair the arithmetic is ste_xattn_mq_fwd's, instruction for instruction
  *   (same bound, same bits as that kernel on the same rows without a mask): a pair's out row depends on
  *   its query row and its segment's rows alone, not on R, G, its position, its tile-mates or where the
- *   segment lies.  R, G, ntile >= 1, else STE_ERR_SHAPE. */
+ *   segment lies.  R, G, ntile >= 1, else STE_ERR_SHAPE.
+ * ste_xattn_seg_mx8_fwd: ste_xattn_seg_fwd on MX-fp8 rows.  k / v point into rows of a [rows][ldkv] buffer
+ *   of OCP e4m3 bytes (ldkv in bytes), ks / vs into the [rows][lds] buffer of their E8M0 block scales: the
+ *   scale of column c of a row's K is ks[row*lds + c/32], of its V vs[row*lds + c/32] (in an
+ *   AudioStateStore v = k + P, ldkv = 2P, vs = ks + P/32, lds = 2P/32).  An element is read as
+ *   bf16(float(e4m3) * 2^(E - 127)) (ste_mx8_dequant) and from there on the arithmetic is
+ *   ste_xattn_seg_fwd's, instruction for instruction: the same bits as that kernel on the dequantised
+ *   rows.  The shape rule of ste_xattn_seg_fwd with P % 32 == 0, ldkv % 8 == 0, lds >= P/32 and k / v
+ *   8-byte aligned, else STE_ERR_SHAPE before any launch. */
 int ste_xattn_mq_fwd(const float* q, const int32_t* qrow, const void* k, const void* v, int64_t ldkv,
                      const int32_t* mask, int B, int C, int S, int P, int nh, float scale, float* out, void* stream);
 int ste_xattn_gather_fwd(const float* q, const int32_t* qrow, const void* k, const void* v, int64_t ldkv,
@@ -480,6 +494,10 @@ int ste_xattn_seg_fwd(const float* q, const int32_t* qrow, const int32_t* pseg, 
                       int64_t ldkv, const int64_t* seg_row, const int32_t* seg_len, const int32_t* tile_first,
                       const int32_t* tile_cnt, int ntile, int R, int G, int P, int nh, float scale, float* out,
                       void* stream);
+int ste_xattn_seg_mx8_fwd(const float* q, const int32_t* qrow, const int32_t* pseg, const void* k, const void* v,
+                          int64_t ldkv, const void* ks, const void* vs, int64_t lds, const int64_t* seg_row,
+                          const int32_t* seg_len, const int32_t* tile_first, const int32_t* tile_cnt, int ntile,
+                          int R, int G, int P, int nh, float scale, float* out, void* stream);
 /* As ste_xattn_bwd, but dk/dv are bf16 and WRITTEN (not accumulated), and colsum_part fp32
  * [B, 2P] receives per-sample column sums of dk (cols [0,P)) and dv (cols [P,2P)) in fp32, for the
  * key/value bias gradient; lddkv % 8 == 0. */

@@ -99,6 +99,19 @@ STE_DEV int mx8_exp(float amax) {
   const float m = frexpf(amax * (1.0f / 448.0f), &e2);  // amax/448 = m·2^e2, m in [0.5, 1)
   return max(-127, min(127, (m == 0.5f) ? e2 - 1 : e2));
 }
+// What 8 stored MX-fp8 bytes mean (ste_mx8_dequant): bf16(float(e4m3)·2^(E - 127)), E the block's
+// E8M0 byte (2^-127 is the fp32 subnormal 0x00400000; E = 255 is NaN).  The fp32 product is exact (4
+// significant bits times a power of two, fp32 subnormals kept), so the only rounding is the final one
+// and only below bf16's normal range.  Plain v_mul_f32: the library is built without packed fp32.
+STE_DEV bf16x8 mx8_dequant8(uint2 b, uint32_t E) {
+  const float s = __builtin_bit_cast(float, E == 0u ? 0x00400000u : E == 255u ? 0x7fc00000u : E << 23);
+  const auto f0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b.x, false), f1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b.x, true);
+  const auto f2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b.y, false), f3 = __builtin_amdgcn_cvt_pk_f32_fp8((int)b.y, true);
+  bf16x8 r;
+  r[0] = (bf16)(f0[0] * s), r[1] = (bf16)(f0[1] * s), r[2] = (bf16)(f1[0] * s), r[3] = (bf16)(f1[1] * s);
+  r[4] = (bf16)(f2[0] * s), r[5] = (bf16)(f2[1] * s), r[6] = (bf16)(f3[0] * s), r[7] = (bf16)(f3[1] * s);
+  return r;
+}
 STE_DEV float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 STE_DEV float swish_f(float x) { return x * sigmoidf_(x); }
 STE_DEV float swish_d(float x) {

@@ -1963,6 +1963,30 @@ extern "C" int ste_mx8_quant(const void* x, int64_t ldx, int rows, int K, void* 
   return 0;
 }
 
+// e4m3 [rows][K] (row stride ld bytes) + E8M0 [rows][K/32] -> bf16 [rows][K] (mx8_dequant8): one lane
+// per 8 elements, 4 lanes per block reading the same scale byte.
+__global__ __launch_bounds__(256) void mx8_dequant_kernel(const uint8_t* q, int64_t ld, int rows, int K,
+                                                          const uint8_t* sc, bf16* out) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int per_row = K >> 3;
+  const int64_t r = t / per_row;
+  const int c = (int)(t - r * per_row) * 8;
+  if (r >= rows) return;
+  const uint2 b = *reinterpret_cast<const uint2*>(q + r * ld + c);
+  *reinterpret_cast<bf16x8*>(out + r * K + c) = mx8_dequant8(b, sc[r * (K >> 5) + (c >> 5)]);
+}
+
+extern "C" int ste_mx8_dequant(const void* q, int64_t ldq, int rows, int K, const void* scales, void* out,
+                               void* stream) {
+  if (rows <= 0 || K <= 0 || (K & 127) || ldq < K || (ldq & 7) || ((uintptr_t)q & 7) || ((uintptr_t)out & 15))
+    return STE_ERR_SHAPE;
+  const int64_t threads = (int64_t)rows * (K >> 3);
+  hipLaunchKernelGGL(mx8_dequant_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const uint8_t*)q, ldq, rows, K, (const uint8_t*)scales, (bf16*)out);
+  STE_CHECK_LAUNCH();
+  return 0;
+}
+
 namespace {
 // Round 5: until the scale-select fix (mfma_mx) the persistent 8-phase MX kernel returned wrong
 // products at every shape it was planned for (>= 240 tiles), in every tree since round 3

@@ -5,7 +5,10 @@
 //                         xattn_fwd_kernel<1> of xattn_fwd.h with gathered addresses;
 //   ste_xattn_seg_fwd     (query, segment) pairs against runs of rows of one K/V buffer (a text query
 //                         against stored corpus clips): the body of ste_xattn_mq_fwd on tiles of
-//                         pairs that share a segment.
+//                         pairs that share a segment;
+//   ste_xattn_seg_mx8_fwd the same on rows stored as MX-fp8 (e4m3 bytes + one E8M0 scale per 32
+//                         columns): a fragment is dequantised to the bf16 values the body already
+//                         takes, so the arithmetic from there on is that of ste_xattn_seg_fwd.
 #include "common.h"
 #include "xattn_fwd.h"
 #include "../../include/ste.h"
@@ -39,10 +42,25 @@ STE_DEV float xrow_max(float v) {
 // DHMAX: head dim rounded up to 32, 64, 128 or 256 (register arrays are sized by it).
 // row: the lane's row of q (-1 = empty slot); k / v: row 0 of the run; mask: the run's key mask or
 // NULL; o: the lane's out row (NULL = no slot), columns from c0 on.  S >= 1.
-template <int DHMAX>
-STE_DEV void xattn_mq_tile(const float* __restrict__ q, int row, const bf16* __restrict__ k,
-                           const bf16* __restrict__ v, int64_t ldkv, const int32_t* __restrict__ mask, int S, int P,
-                           int dh, int c0, float scale, float* __restrict__ o) {
+// MX: k / v are e4m3 bytes (ldkv in bytes) and ks / vs row 0 of their E8M0 scales (row stride lds
+// bytes, one byte per 32 columns of the WHOLE row, so column c0 + d has scale byte (c0 + d) / 32).
+// c0 + d is a multiple of 8 at every fragment, so its 8 columns lie in one block: 8 bytes and one
+// scale byte become the bf16x8 the bf16 path loads (mx8_dequant8) and nothing after it differs.
+template <bool MX>
+STE_DEV bf16x8 xattn_load8(const void* base, int64_t ld, const uint8_t* sc, int64_t lds, int64_t r, int col) {
+  if constexpr (MX) {
+    const uint2 b = *reinterpret_cast<const uint2*>(static_cast<const uint8_t*>(base) + r * ld + col);
+    return mx8_dequant8(b, sc[r * lds + (col >> 5)]);
+  } else {
+    return *reinterpret_cast<const bf16x8*>(static_cast<const bf16*>(base) + r * ld + col);
+  }
+}
+
+template <int DHMAX, bool MX = false>
+STE_DEV void xattn_mq_tile(const float* __restrict__ q, int row, const void* __restrict__ k,
+                           const void* __restrict__ v, int64_t ldkv, const uint8_t* __restrict__ ks,
+                           const uint8_t* __restrict__ vs, int64_t lds, const int32_t* __restrict__ mask, int S,
+                           int P, int dh, int c0, float scale, float* __restrict__ o) {
   constexpr int NDS = DHMAX / 32;                 // d steps of Q·Kᵀ
   constexpr int NCT = DHMAX / 16;                 // 16-column tiles of out
   constexpr int VC = DHMAX < 128 ? DHMAX : 128;   // V columns staged at a time
@@ -85,13 +103,12 @@ STE_DEV void xattn_mq_tile(const float* __restrict__ q, int row, const bf16* __r
 #pragma unroll
     for (int hf = 0; hf < 2; ++hf) {
       const int key = min(s0 + 16 * hf + li, S - 1);  // rows past S are masked below
-      const bf16* kr = k + (int64_t)key * ldkv + c0;
       f32x4 a = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int ds = 0; ds < NDS; ++ds) {
         const int d = 32 * ds + 8 * g;
         if (32 * ds < dh) {
-          const bf16x8 kf = d < dh ? *reinterpret_cast<const bf16x8*>(kr + d) : zero8;
+          const bf16x8 kf = d < dh ? xattn_load8<MX>(k, ldkv, ks, lds, key, c0 + d) : zero8;
           a = mfma16(kf, qh[ds], a);
           a = mfma16(kf, ql[ds], a);
         }
@@ -135,7 +152,7 @@ STE_DEV void xattn_mq_tile(const float* __restrict__ q, int row, const bf16* __r
           const int col = cb + 8 * cc;
           bf16x8 x = zero8;
           if (s0 + kr < S && col < dh)
-            x = *reinterpret_cast<const bf16x8*>(v + (int64_t)(s0 + kr) * ldkv + c0 + col);
+            x = xattn_load8<MX>(v, ldkv, vs, lds, s0 + kr, c0 + col);
           *reinterpret_cast<bf16x8*>(vt + (kr * VLD + 8 * cc) * 2) = x;
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
@@ -198,7 +215,7 @@ __global__ __launch_bounds__(NT) void xattn_mq_kernel(const float* __restrict__ 
   const int dh = P / nh, c0 = hh * dh;
   const int c = qt * 16 + (threadIdx.x & 15);  // this lane's query slot
   const int row = c < C ? qrow[(int64_t)b * C + c] : -1;
-  xattn_mq_tile<DHMAX>(q, row, k + (int64_t)b * S * ldkv, v + (int64_t)b * S * ldkv, ldkv,
+  xattn_mq_tile<DHMAX>(q, row, k + (int64_t)b * S * ldkv, v + (int64_t)b * S * ldkv, ldkv, nullptr, nullptr, 0,
                        mask ? mask + (int64_t)b * S : nullptr, S, P, dh, c0, scale,
                        c < C ? out + ((int64_t)b * C + c) * P + c0 : nullptr);
 }
@@ -206,11 +223,14 @@ __global__ __launch_bounds__(NT) void xattn_mq_kernel(const float* __restrict__ 
 // ste_xattn_seg_fwd: one block per (tile, head hh).  Tile t is the cnt <= 16 consecutive pairs from
 // tile_first[t] on, all of segment pseg[tile_first[t]]: rows seg_row[g] .. seg_row[g] + seg_len[g] - 1
 // of k / v.  An empty tile (count 0) or a tile of an empty or negative segment returns before it
-// reads a key: its out rows keep the zeros the host wrote.
-template <int DHMAX>
+// reads a key: its out rows keep the zeros the host wrote.  MX: k / v are e4m3 bytes with the
+// scales ks / vs (xattn_mq_tile), else bf16 (ks = vs = NULL); ldkv in elements of either.
+template <int DHMAX, bool MX>
 __global__ __launch_bounds__(NT) void xattn_seg_kernel(const float* __restrict__ q, const int32_t* __restrict__ qrow,
-                                                     const int32_t* __restrict__ pseg, const bf16* __restrict__ k,
-                                                     const bf16* __restrict__ v, int64_t ldkv,
+                                                     const int32_t* __restrict__ pseg, const void* __restrict__ k,
+                                                     const void* __restrict__ v, int64_t ldkv,
+                                                     const uint8_t* __restrict__ ks,
+                                                     const uint8_t* __restrict__ vs, int64_t lds,
                                                      const int64_t* __restrict__ seg_row,
                                                      const int32_t* __restrict__ seg_len,
                                                      const int32_t* __restrict__ tile_first,
@@ -227,9 +247,10 @@ __global__ __launch_bounds__(NT) void xattn_seg_kernel(const float* __restrict__
   const int c = threadIdx.x & 15;
   const int r = first + c;
   const int row = c < cnt ? qrow[r] : -1;
-  const int64_t base = seg_row[g] * ldkv;
-  xattn_mq_tile<DHMAX>(q, row, k + base, v + base, ldkv, nullptr, S, P, dh, c0, scale,
-                       c < cnt ? out + (int64_t)r * P + c0 : nullptr);
+  const int64_t base = seg_row[g] * ldkv * (MX ? 1 : 2), sbase = MX ? seg_row[g] * lds : 0;  // bytes
+  xattn_mq_tile<DHMAX, MX>(q, row, static_cast<const char*>(k) + base, static_cast<const char*>(v) + base, ldkv,
+                           ks + sbase, vs + sbase, lds, nullptr, S, P, dh, c0, scale,
+                           c < cnt ? out + (int64_t)r * P + c0 : nullptr);
 }
 
 // the rule of ste_xattn_fwd (heads.hip), without its cap on S
@@ -275,13 +296,13 @@ extern "C" int ste_xattn_gather_fwd(const float* q, const int32_t* qrow, const v
   return 0;
 }
 
-extern "C" int ste_xattn_seg_fwd(const float* q, const int32_t* qrow, const int32_t* pseg, const void* k,
-                                 const void* v, int64_t ldkv, const int64_t* seg_row, const int32_t* seg_len,
-                                 const int32_t* tile_first, const int32_t* tile_cnt, int NTILE, int R, int G, int P,
-                                 int nh, float scale, float* out, void* stream) {
-  if (R <= 0 || G <= 0 || NTILE <= 0 || !xattn_dims_ok(P, nh) || (ldkv & 7) || ldkv < P ||
-      (((uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15))
-    return STE_ERR_SHAPE;
+namespace {
+// the launch shared by ste_xattn_seg_fwd (MX = false) and ste_xattn_seg_mx8_fwd, arguments checked
+template <bool MX>
+int xattn_seg_launch(const float* q, const int32_t* qrow, const int32_t* pseg, const void* k, const void* v,
+                     int64_t ldkv, const uint8_t* ks, const uint8_t* vs, int64_t lds, const int64_t* seg_row,
+                     const int32_t* seg_len, const int32_t* tile_first, const int32_t* tile_cnt, int NTILE, int R,
+                     int G, int P, int nh, float scale, float* out, void* stream) {
   const int dh = P / nh;
   const int64_t blocks = (int64_t)NTILE * nh;
   if (blocks > 0x7fffffff) return STE_ERR_SHAPE;
@@ -289,9 +310,8 @@ extern "C" int ste_xattn_seg_fwd(const float* q, const int32_t* qrow, const int3
   hipError_t e = hipMemsetAsync(out, 0, (size_t)R * P * sizeof(float), (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
 #define STE_SEG_LAUNCH(D)                                                                                      \
-  hipLaunchKernelGGL(xattn_seg_kernel<D>, dim3((unsigned)blocks), dim3(NT), 0, (hipStream_t)stream, q, qrow, \
-                     pseg, (const bf16*)k, (const bf16*)v, ldkv, seg_row, seg_len, tile_first, tile_cnt, R, G, P, \
-                     nh, scale, out)
+  hipLaunchKernelGGL((xattn_seg_kernel<D, MX>), dim3((unsigned)blocks), dim3(NT), 0, (hipStream_t)stream, q, qrow, \
+                     pseg, k, v, ldkv, ks, vs, lds, seg_row, seg_len, tile_first, tile_cnt, R, G, P, nh, scale, out)
   if (dh <= 32) STE_SEG_LAUNCH(32);
   else if (dh <= 64) STE_SEG_LAUNCH(64);
   else if (dh <= 128) STE_SEG_LAUNCH(128);
@@ -299,4 +319,28 @@ extern "C" int ste_xattn_seg_fwd(const float* q, const int32_t* qrow, const int3
 #undef STE_SEG_LAUNCH
   STE_CHECK_LAUNCH();
   return 0;
+}
+}  // namespace
+
+extern "C" int ste_xattn_seg_fwd(const float* q, const int32_t* qrow, const int32_t* pseg, const void* k,
+                                 const void* v, int64_t ldkv, const int64_t* seg_row, const int32_t* seg_len,
+                                 const int32_t* tile_first, const int32_t* tile_cnt, int NTILE, int R, int G, int P,
+                                 int nh, float scale, float* out, void* stream) {
+  if (R <= 0 || G <= 0 || NTILE <= 0 || !xattn_dims_ok(P, nh) || (ldkv & 7) || ldkv < P ||
+      (((uintptr_t)k | (uintptr_t)v | (uintptr_t)out) & 15))
+    return STE_ERR_SHAPE;
+  return xattn_seg_launch<false>(q, qrow, pseg, k, v, ldkv, nullptr, nullptr, 0, seg_row, seg_len, tile_first,
+                                 tile_cnt, NTILE, R, G, P, nh, scale, out, stream);
+}
+
+extern "C" int ste_xattn_seg_mx8_fwd(const float* q, const int32_t* qrow, const int32_t* pseg, const void* k,
+                                     const void* v, int64_t ldkv, const void* ks, const void* vs, int64_t lds,
+                                     const int64_t* seg_row, const int32_t* seg_len, const int32_t* tile_first,
+                                     const int32_t* tile_cnt, int NTILE, int R, int G, int P, int nh, float scale,
+                                     float* out, void* stream) {
+  if (R <= 0 || G <= 0 || NTILE <= 0 || !xattn_dims_ok(P, nh) || (P & 31) || (ldkv & 7) || ldkv < P ||
+      lds < P / 32 || !ks || !vs || (((uintptr_t)k | (uintptr_t)v) & 7) || ((uintptr_t)out & 15))
+    return STE_ERR_SHAPE;
+  return xattn_seg_launch<true>(q, qrow, pseg, k, v, ldkv, (const uint8_t*)ks, (const uint8_t*)vs, lds, seg_row,
+                                seg_len, tile_first, tile_cnt, NTILE, R, G, P, nh, scale, out, stream);
 }

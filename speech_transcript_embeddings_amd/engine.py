@@ -1319,8 +1319,13 @@ class Engine:
         live = torch.where(pseg < 0, pseg, torch.arange(R, device=dev, dtype=torch.int32))
         tcat, acat = self._e(R, 2 * P), self._e(R, 2 * P)
         att = self._e(R, P)
-        ops.xattn_seg_fwd(qt, qrow, pseg, store.kv[:, :P], store.kv[:, P:], store.seg_row.index_select(0, clips),
-                          store.frames.index_select(0, clips), plan["tile_first"], plan["tile_cnt"], nh, att)
+        seg = (store.seg_row.index_select(0, clips), store.frames.index_select(0, clips), plan["tile_first"],
+               plan["tile_cnt"], nh, att)
+        if store.kv_dtype == "mx8":   # the same pairs over the stored e4m3 bytes and their block scales
+            ops.xattn_seg_mx8_fwd(qt, qrow, pseg, store.kv[:, :P], store.kv[:, P:], store.kv_scales[:, :P // 32],
+                                  store.kv_scales[:, P // 32:], *seg)
+        else:
+            ops.xattn_seg_fwd(qt, qrow, pseg, store.kv[:, :P], store.kv[:, P:], *seg)
         ops.linear(att, self._w32("text_to_audio_attention.out_proj.weight"),
                    s.p("text_to_audio_attention.out_proj.bias"), out=tcat[:, P:])
         ops.copy2d(tcat[:, :P], tproj.index_select(0, qrow.clamp(min=0).long()))

@@ -241,6 +241,19 @@ def mx8_quant(x, q=None, scales=None):
     return q, scales
 
 
+def mx8_dequant(q, scales, out=None):
+    """(e4m3 bytes [rows, K], E8M0 scales [rows, K/32]) -> bf16 [rows, K], what the stored bytes mean:
+    bf16(float(e4m3) * 2^(E - 127)) (ste_mx8_dequant).  q may be a row-strided view."""
+    rows, K = q.shape
+    assert q.dtype == torch.uint8 and scales.dtype == torch.uint8 and q.stride(-1) == 1
+    assert scales.shape == (rows, K // 32) and scales.is_contiguous()
+    if out is None:
+        out = torch.empty((rows, K), device=q.device, dtype=BF16)
+    assert out.dtype == BF16 and out.shape == (rows, K) and out.is_contiguous()
+    call("ste_mx8_dequant", ptr(q), _ld(q), rows, K, ptr(scales), ptr(out), _s())
+    return out
+
+
 def linear_mx8(xq, wq, bias=None, q_out=None, **kw):
     """y = x·wᵀ (+bias) on the MX-fp8 GEMM: xq = (e4m3 [M,K], scales), wq = (e4m3 [N,K], scales).
     q_out = (e4m3 [M,N], scales [M,N/32]): also write y MX-fp8 quantised; with out=False only that."""
@@ -706,6 +719,26 @@ def xattn_seg_fwd(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, n
     assert k.dtype == BF16 and v.dtype == BF16 and _ld(k) == _ld(v)
     call("ste_xattn_seg_fwd", ptr(q), ptr(qrow), ptr(pseg), ptr(k), ptr(v), _ld(k), ptr(seg_row), ptr(seg_len),
          ptr(tile_first), ptr(tile_cnt), tile_first.numel(), R, G, P, nh, float((P // nh) ** -0.5), ptr(out), _s())
+
+
+def xattn_seg_mx8_fwd(q, qrow, pseg, k, v, ks, vs, seg_row, seg_len, tile_first, tile_cnt, nh, out):
+    """xattn_seg_fwd on MX-fp8 rows: k / v uint8 views [rows, P] of one buffer of e4m3 bytes, ks / vs
+    uint8 views [rows, P/32] of the buffer of their E8M0 scales (an AudioStateStore's kv[:, :P],
+    kv[:, P:], kv_scales[:, :P/32], kv_scales[:, P/32:]).  The same bits as xattn_seg_fwd on the
+    mx8_dequant of those rows."""
+    P = q.shape[-1]
+    R, G = qrow.numel(), seg_row.numel()
+    assert q.dtype == F32 and q.is_contiguous() and out.dtype == F32 and out.shape == (R, P) and out.is_contiguous()
+    assert qrow.dtype == torch.int32 and pseg.dtype == torch.int32 and pseg.numel() == R
+    assert seg_row.dtype == torch.int64 and seg_len.dtype == torch.int32 and seg_len.numel() == G
+    assert tile_first.dtype == torch.int32 and tile_cnt.dtype == torch.int32
+    assert tile_first.numel() == tile_cnt.numel()
+    assert all(t.is_contiguous() for t in (qrow, pseg, seg_row, seg_len, tile_first, tile_cnt))
+    assert k.dtype == torch.uint8 and v.dtype == torch.uint8 and _ld(k) == _ld(v)
+    assert ks.dtype == torch.uint8 and vs.dtype == torch.uint8 and _ld(ks) == _ld(vs)
+    call("ste_xattn_seg_mx8_fwd", ptr(q), ptr(qrow), ptr(pseg), ptr(k), ptr(v), _ld(k), ptr(ks), ptr(vs), _ld(ks),
+         ptr(seg_row), ptr(seg_len), ptr(tile_first), ptr(tile_cnt), tile_first.numel(), R, G, P, nh,
+         float((P // nh) ** -0.5), ptr(out), _s())
 
 
 def xattn_bwd(q, k, v, probs, dout, B, S, nh, dq, dk, dv, seeds, drop_p=0.0, colsum=None, mask=None):

@@ -25,6 +25,8 @@ The other direction, a typed phrase against the corpus of clips, n
 of every clip; they are computed once when the corpus is indexed and attended over in place:
 
     AudioStateStore(model): add(input_values, mask), len(), frames, nbytes, search(text_emb, k)
+    AudioStateStore(model, kv_dtype="mx8"): the K/V rows as MX-fp8 at 0.516 of the bytes (DESIGN §19);
+        kv_rows(n), kv_bytes_per_frame(dim, kv_dtype)
     plan_clip_pairs(idx)                          -> the (query, clip) pairs grouped by clip, in tiles
     rerank_clips(model, input_ids, attention_mask, store, idx) -> (values, indices)
     evaluate_retrieval(..., rerank_k=k, rerank_t2a=True) -> also "t2a_rerank"
@@ -236,6 +238,20 @@ def plan_clip_pairs(idx: torch.Tensor) -> dict:
                 tile_first=tile_first.to(I32), tile_cnt=tile_cnt.to(I32))
 
 
+KV_DTYPES = ("bf16", "mx8")
+
+
+def kv_bytes_per_frame(dim: int, kv_dtype: str = "bf16") -> int:
+    """Bytes an AudioStateStore of projection width dim holds per stored frame (one K|V row of 2·dim
+    columns): "bf16" 4·dim (3,072 at dim = 768); "mx8" 2·dim e4m3 bytes + 2·dim/32 E8M0 scale bytes
+    (1,584 at dim = 768, 0.516 of bf16)."""
+    if kv_dtype == "bf16":
+        return 4 * dim
+    if kv_dtype == "mx8":
+        return 2 * dim + 2 * dim // 32
+    raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
+
+
 class AudioStateStore:
     """What the text -> audio fused pair score needs of every corpus clip, computed once when the
     corpus is indexed: the clip's projection aproj fp32 [P], its unit row (in an
@@ -246,17 +262,36 @@ class AudioStateStore:
     audio mask must be a prefix mask with at least one valid frame, else ValueError.  3 KB per frame
     at P = 768: 1.5 MB per 10 s clip.  Without use_cross_modal only aproj and the unit rows are kept.
 
+    kv_dtype selects how the K|V rows are held (kv_bytes_per_frame):
+      "bf16"  kv bf16 [capacity, 2P]: 4P bytes per frame, 3,072 at P = 768 (the default);
+      "mx8"   kv uint8 [capacity, 2P] of OCP e4m3 bytes + kv_scales uint8 [capacity, 2P/32] of E8M0
+              block scales (one per 32 columns), ops.mx8_quant of each bf16 row as it is added:
+              2P + P/16 bytes per frame, 1,584 at P = 768 (0.516 of bf16).  ste_xattn_seg_mx8_fwd
+              attends over the bytes in place.  Quantisation is per row, so a clip's bytes depend on
+              its bf16 rows alone.  Needs P % 64 == 0, else ValueError.
+    kv_rows(n) says what clip n's stored rows mean, as bf16, for either.
+
     The store is valid for the weights it was built with: it records the model's
     ParamStore.weights_token() at the first add, and adding to or scoring against it after the
     weights changed raises RuntimeError (check)."""
 
-    def __init__(self, model, device="cuda", index_dtype: torch.dtype = F32, reserve_frames: int = 0):
+    def __init__(self, model, device="cuda", index_dtype: torch.dtype = F32, reserve_frames: int = 0,
+                 kv_dtype: str = "bf16"):
         self.model, self.device = model, torch.device(device)
         self.dim = int(model.projection_dim)
         self.fused = bool(getattr(model, "use_cross_modal", False))
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
+        if kv_dtype == "mx8" and self.fused and self.dim % 64:
+            raise ValueError(f'kv_dtype="mx8" needs projection_dim % 64 == 0 (MX blocks of 32 over the 2P columns, '
+                             f"quantised 128 at a time), got {self.dim}")
+        self.kv_dtype = kv_dtype
         self.index = EmbeddingIndex(self.dim, index_dtype, self.device)
-        self.kv = torch.empty(max(int(reserve_frames), 0) if self.fused else 0, 2 * self.dim, device=self.device,
-                              dtype=BF16)
+        cap = max(int(reserve_frames), 0) if self.fused else 0
+        mx8 = kv_dtype == "mx8"
+        self.kv = torch.empty(cap, 2 * self.dim, device=self.device, dtype=torch.uint8 if mx8 else BF16)
+        # the E8M0 block scales of kv's rows (mx8 only): grown together with kv
+        self.kv_scales = torch.empty(cap, 2 * self.dim // 32, device=self.device, dtype=torch.uint8) if mx8 else None
         self.rows = 0                         # rows of kv in use
         self._seg_row: list[int] = []
         self._seg_len: list[int] = []
@@ -275,9 +310,14 @@ class AudioStateStore:
     def _reserve(self, rows: int) -> None:
         if rows <= self.kv.shape[0]:
             return
-        grown = torch.empty(max(rows, 2 * self.kv.shape[0]), self.kv.shape[1], device=self.device, dtype=BF16)
+        cap = max(rows, 2 * self.kv.shape[0])
+        grown = torch.empty(cap, self.kv.shape[1], device=self.device, dtype=self.kv.dtype)
         grown[:self.rows].copy_(self.kv[:self.rows])
         self.kv = grown
+        if self.kv_scales is not None:
+            grown = torch.empty(cap, self.kv_scales.shape[1], device=self.device, dtype=torch.uint8)
+            grown[:self.rows].copy_(self.kv_scales[:self.rows])
+            self.kv_scales = grown
 
     @torch.no_grad()
     def add(self, input_values, attention_mask_audio=None, *, audio_encoded=None) -> None:
@@ -314,13 +354,16 @@ class AudioStateStore:
                                 torch.empty(B * T, Ha, device=self.device, dtype=BF16))
             kv = eng._kv("text_to_audio_attention", "audio_seq_to_projection", ahb)[0]
             self._reserve(self.rows + sum(frames))
-            if all(n == T for n in frames):
-                self.kv[self.rows:self.rows + B * T].copy_(kv)
-            else:
-                at = self.rows
-                for b, n in enumerate(frames):
-                    self.kv[at:at + n].copy_(kv[b * T:b * T + n])
-                    at += n
+            # (source, destination): the bf16 rows, or their e4m3 bytes and E8M0 scales
+            pairs = [(kv, self.kv)] if self.kv_scales is None else list(zip(ops.mx8_quant(kv), (self.kv, self.kv_scales)))
+            for src, dst in pairs:
+                if all(n == T for n in frames):
+                    dst[self.rows:self.rows + B * T].copy_(src)
+                else:
+                    at = self.rows
+                    for b, n in enumerate(frames):
+                        dst[at:at + n].copy_(src[b * T:b * T + n])
+                        at += n
         for n in frames:
             self._seg_row.append(self.rows)
             self._seg_len.append(n)
@@ -359,8 +402,19 @@ class AudioStateStore:
     def nbytes(self) -> int:
         """Bytes held for the clips added so far (the K/V rows in use, aproj, the unit rows and the segment table)."""
         n = len(self)
-        return (self.rows * self.kv.shape[1] * 2 + n * self.dim * 4
+        return (self.rows * kv_bytes_per_frame(self.dim, self.kv_dtype) + n * self.dim * 4
                 + n * self.dim * (2 if self.index.dtype == BF16 else 4) + n * 12)
+
+    def kv_rows(self, n: int) -> torch.Tensor:
+        """Clip n's stored K|V rows as bf16 [frames, 2P]: a slice of kv for "bf16" (a view), what the
+        stored bytes mean (ops.mx8_dequant) for "mx8"."""
+        if not self.fused:
+            raise ValueError("the store keeps no K/V rows without use_cross_modal")
+        a = self._seg_row[n]
+        b = a + self._seg_len[n]
+        if self.kv_scales is None:
+            return self.kv[a:b]
+        return ops.mx8_dequant(self.kv[a:b], self.kv_scales[a:b])
 
     def search(self, text_emb: torch.Tensor, k: int):
         """Stage 1: (values fp32 [Q, k], indices int32 [Q, k]) of the k best clips per unit text row,
@@ -385,7 +439,8 @@ def _pad_rows(chunks, fill):
 
 @torch.no_grad()
 def evaluate_retrieval(model, data_loader, device, ks=(1, 5, 10), index_dtype: torch.dtype = F32,
-                       return_ranks: bool = False, rerank_k: int = 0, rerank_t2a: bool = False) -> dict:
+                       return_ranks: bool = False, rerank_k: int = 0, rerank_t2a: bool = False,
+                       store_kv_dtype: str = "bf16") -> dict:
     """One pass over a loader of the reference's batch dicts (custom_collate_fn's keys): embeds the
     clean transcripts and the audio, indexes both and ranks pair i's partner for query i in both
     directions.  Returns {"a2t": retrieval_metrics, "t2a": retrieval_metrics} (audio -> text,
@@ -406,7 +461,8 @@ def evaluate_retrieval(model, data_loader, device, ks=(1, 5, 10), index_dtype: t
     "t2a_rerank_ranks"), the other direction: the first pass also fills an AudioStateStore with the
     clips' audio states, and after it each batch of clean transcripts (the kept token rows) is
     reranked against store.search(text_emb, rerank_k) with rerank_clips.  This direction needs no
-    further loader pass.  With the flag off nothing changes.
+    further loader pass.  With the flag off nothing changes.  store_kv_dtype is that store's kv_dtype
+    ("bf16", or "mx8" for MX-fp8 rows at about half the bytes).
     Out of scope: the model_infer.py variant, a cache of the corpus text K/V, and any backward."""
     model.eval()
     do_rerank = rerank_k > 0 and getattr(model, "use_cross_modal", False)
@@ -427,7 +483,7 @@ def evaluate_retrieval(model, data_loader, device, ks=(1, 5, 10), index_dtype: t
             enc = model.encode_audio(b["input_values"], b.get("attention_mask_audio"))
             a = _unit_rows(enc[0])
             if store is None:
-                store = AudioStateStore(model, a.device, index_dtype)
+                store = AudioStateStore(model, a.device, index_dtype, kv_dtype=store_kv_dtype)
             store.add(b["input_values"], b.get("attention_mask_audio"), audio_encoded=enc)   # indexes a as well
         else:
             a = embed_audio(model, b["input_values"], b.get("attention_mask_audio"))

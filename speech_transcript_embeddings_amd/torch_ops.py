@@ -26,6 +26,8 @@ through them); the fused training step itself calls the C ABI directly (engine.p
         CrossModalAttention core (ref :125-168) for C candidate queries per clip sharing its keys/values
     ste::xattn_seg(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, nh) -> out
         the same core for (text query, stored corpus clip) pairs: segments of one K/V buffer
+    ste::xattn_seg_mx8(q, qrow, pseg, k, v, ks, vs, seg_row, seg_len, tile_first, tile_cnt, nh) -> out
+        ste::xattn_seg on rows stored as MX-fp8 bytes and E8M0 block scales (DESIGN §19)
     ste::align_matrix(q, kv, kmask?, nh) -> (matrix, emit, out)
         WordLevelAlignmentModule's head-averaged alignment_matrix (ref :295), its frame-major log, the output
     ste::align_decode(emit, ntok, nfrm) -> (spans, score)
@@ -331,6 +333,29 @@ def _xattn_seg_fake(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt,
     return q.new_empty(qrow.numel(), q.shape[-1], dtype=F32)
 
 
+@torch.library.custom_op("ste::xattn_seg_mx8", mutates_args=())
+def xattn_seg_mx8(q: Tensor, qrow: Tensor, pseg: Tensor, k: Tensor, v: Tensor, ks: Tensor, vs: Tensor,
+                  seg_row: Tensor, seg_len: Tensor, tile_first: Tensor, tile_cnt: Tensor, nh: int) -> Tensor:
+    """ste::xattn_seg on MX-fp8 rows (forward only): k / v uint8 [rows, P] (OCP e4m3 bytes, views of one
+    buffer), ks / vs uint8 [rows, P/32] (their E8M0 block scales, views of one buffer); the other
+    operands and out fp32 [R, P] as ste::xattn_seg.  The same bits as ste::xattn_seg on the dequantised
+    rows (ops.mx8_dequant)."""
+    out = torch.empty(qrow.numel(), q.shape[-1], device=q.device, dtype=F32)
+
+    def i32(t):
+        return t.reshape(-1).to(torch.int32).contiguous()
+
+    ops.xattn_seg_mx8_fwd(q.float().contiguous(), i32(qrow), i32(pseg), k, v, ks, vs,
+                          seg_row.reshape(-1).to(torch.int64).contiguous(), i32(seg_len), i32(tile_first),
+                          i32(tile_cnt), int(nh), out)
+    return out
+
+
+@xattn_seg_mx8.register_fake
+def _xattn_seg_mx8_fake(q, qrow, pseg, k, v, ks, vs, seg_row, seg_len, tile_first, tile_cnt, nh):
+    return q.new_empty(qrow.numel(), q.shape[-1], dtype=F32)
+
+
 # -------------------------------------------------------------------- alignment
 @torch.library.custom_op("ste::align_matrix", mutates_args=())
 def align_matrix(q: Tensor, kv: Tensor, kmask: Optional[Tensor], nh: int) -> tuple[Tensor, Tensor, Tensor]:
@@ -374,4 +399,4 @@ def _align_decode_fake(emit, ntok, nfrm):
 
 
 OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim", "xattn_mq",
-       "xattn_seg", "align_matrix", "align_decode")
+       "xattn_seg", "xattn_seg_mx8", "align_matrix", "align_decode")
