@@ -540,6 +540,30 @@ int ste_rank1_bwd(const float* a, const float* w, const void* z, int M, int K, i
 int ste_align_matrix_fwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const int32_t* kmask, int B, int L,
                          int T, int P, int nh, float* matrix, float* emit, int64_t lde, void* out, int64_t ldo,
                          void* stream);
+/* ste_align_matrix_fwd for R (query, segment) pairs over runs of rows of ONE K/V buffer (a store of
+ * corpus clips' valid frames).  q bf16 [U*L, ldq]: U query blocks of L token rows; pair r
+ * is query block qblk[r] (int32 [R]) against rows seg_row[g] .. seg_row[g] + seg_len[g] - 1 of kv bf16
+ * [rows, ldkv] = [K | V], g = pseg[r] (int32 [R]); seg_row int64 [G] (every row address is 64-bit),
+ * seg_len int32 [G]; Tmax = the largest segment length among the pairs.  No mask operand: only valid
+ * rows are stored.  Outputs, each optional (all three NULL: STE_ERR_ARG):
+ *   matrix fp32 [R, L, Tmax], emit fp32 [R, Tmax, lde] (frame-major, lde >= L), out bf16 [R*L, ldo].
+ * With F = seg_len[pseg[r]] the pair's arithmetic is ste_align_matrix_fwd's at T = F, thread for
+ * thread: its rows [:F] of matrix, emit and out are bit-identical to ste_align_matrix_fwd(B = 1,
+ * T = F, kmask = NULL) on that query block and a copy of those rows, whatever R, G, Tmax, the pair's
+ * position, the other outputs requested and where the segment lies.  Frames t >= F of matrix and
+ * emit, and columns l >= L of emit, are not written.  An empty pair (qblk[r] < 0, pseg[r] outside
+ * [0, G), seg_len == 0 or seg_len > Tmax) gets zero out rows, reads no row of q or kv and leaves
+ * its matrix and emit rows untouched; it is no error.
+ * Tmax <= 2048 (16·Tmax·4 B of dynamic LDS on top of 8 KiB static, checked against the device's
+ * per-block limit), d = P/nh <= 256, d % 8 == 0, R, G, L >= 1, ldq >= P, ldkv >= 2P, ldkv % 8 == 0, kv
+ * 16-B aligned, Tmax·ldkv + 2P < 2^31 (a segment's elements are addressed by 32-bit
+ * offsets from its first row), lde >= L, ldo >= P; otherwise STE_ERR_SHAPE.  A NULL q, qblk, pseg, kv, seg_row or
+ * seg_len is STE_ERR_ARG.  All of these come before any launch.  The pair rides a grid dimension:
+ * beyond 65535 pairs the entry point issues several launches itself.  No atomics, no workspace. */
+int ste_align_matrix_seg_fwd(const void* q, int64_t ldq, const int32_t* qblk, const int32_t* pseg, const void* kv,
+                             int64_t ldkv, const int64_t* seg_row, const int32_t* seg_len, int R, int G, int L,
+                             int Tmax, int P, int nh, float* matrix, float* emit, int64_t lde, void* out, int64_t ldo,
+                             void* stream);
 /* Monotone (Viterbi) decode of frame-major emissions emit fp32 [B, T, lde] into one frame span per
  * token.  Pair b has tokens 0..n-1 (n = ntok[b]) and frames 0..F-1 (F = nfrm[b]); the path l(t)
  * maximises Σ_t emit[b][t][l(t)] under l(0) = 0, l(F-1) = n-1, l(t) - l(t-1) in {0, 1}.  The

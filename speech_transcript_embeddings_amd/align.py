@@ -57,33 +57,77 @@ def align_infer(eng, th, thb, ahb, b, L, T, ctx, *, want_matrix=False, want_emit
     confidence — the head-averaged alignment matrix (ref:295) — and its frame-major log for
     ops.align_decode.  No [b, nh, L, T] probabilities buffer is allocated.
     -> (scores fp32 [b, L], matrix fp32 [b, L, T] or None, emit fp32 [b, T, L] or None)."""
-    s = eng.s
-    m = eng.m
-    P = m.projection_dim
-    nh = m.word_level_alignment.num_heads
-    W = s.w(PRE + "alignment_attention.in_proj_weight")
-    bW = s.p(PRE + "alignment_attention.in_proj_bias")
-    tp = ops.linear(thb, s.w(PRE + "text_projection.weight"), s.p(PRE + "text_projection.bias"), out_bf16=True)
-    ap = ops.linear(ahb, s.w(PRE + "audio_projection.weight"), s.p(PRE + "audio_projection.bias"), out_bf16=True)
-    q = ops.linear(tp, W[:P], bW[:P], out_bf16=True)
-    kv = ops.linear(ap, W[P:], bW[P:], out_bf16=True)
+    P = eng.m.projection_dim
+    nh = eng.m.word_level_alignment.num_heads
+    q = text_queries(eng, thb)
+    kv = audio_kv(eng, ahb)
     matrix = eng._e(b, L, T) if want_matrix else None
     emit = eng._e(b, T, L) if want_emit else None
     att = eng._e(b * L, P, dtype=BF16)
     ops.align_matrix_fwd(q, kv, ctx["a_mask32"], b, L, T, nh, matrix=matrix, emit=emit, out=att)
+    return confidence_tail(eng, att, th[: b * L], ctx["_tmask_i64"], b * L).view(b, L), matrix, emit
+
+
+def text_queries(eng, thb):
+    """The head's bf16 queries [rows, P] of bf16 text hidden rows: text_projection, then the query
+    third of the attention's in_proj."""
+    s = eng.s
+    P = eng.m.projection_dim
+    tp = ops.linear(thb, s.w(PRE + "text_projection.weight"), s.p(PRE + "text_projection.bias"), out_bf16=True)
+    return ops.linear(tp, s.w(PRE + "alignment_attention.in_proj_weight")[:P],
+                      s.p(PRE + "alignment_attention.in_proj_bias")[:P], out_bf16=True)
+
+
+def audio_kv(eng, ahb):
+    """The head's bf16 K|V rows [rows, 2P] of bf16 audio hidden rows: audio_projection, then the key
+    and value thirds of in_proj in one GEMM.  A row depends on its own frame alone, which is what
+    lets an AudioStateStore keep the rows of a clip's valid frames."""
+    s = eng.s
+    P = eng.m.projection_dim
+    ap = ops.linear(ahb, s.w(PRE + "audio_projection.weight"), s.p(PRE + "audio_projection.bias"), out_bf16=True)
+    return ops.linear(ap, s.w(PRE + "alignment_attention.in_proj_weight")[P:],
+                      s.p(PRE + "alignment_attention.in_proj_bias")[P:], out_bf16=True)
+
+
+def confidence_tail(eng, att, th_rows, tmask_i64, n):
+    """What follows the attention output att bf16 [n, P]: out_proj -> LN(text hidden + output_projection)
+    -> confidence MLP -> x text mask.  th_rows fp32 [n, Ht] are the rows' text hidden states,
+    tmask_i64 their int64 mask (its first n entries).  -> scores fp32 [n]."""
+    s = eng.s
+    P = eng.m.projection_dim
     o2 = ops.linear(att, s.w(PRE + "alignment_attention.out_proj.weight"),
                     s.p(PRE + "alignment_attention.out_proj.bias"), out_bf16=True)
     y = ops.linear(o2, s.w(PRE + "output_projection.weight"), s.p(PRE + "output_projection.bias"),
-                   residual=th[: b * L])
-    aligned_b = eng._e(b * L, P, dtype=BF16)
+                   residual=th_rows)
+    aligned_b = eng._e(n, P, dtype=BF16)
     eng._ln(y, PRE + "layer_norm", 1e-5, yb=aligned_b)
     c1 = ops.linear(aligned_b, s.w(PRE + "alignment_confidence.0.weight"), s.p(PRE + "alignment_confidence.0.bias"),
                     act=ACT_RELU, out_bf16=True)
-    tmask = eng._e(b * L)
-    _lib.call("ste_mask_i64_to_f32", ctx["_tmask_i64"].data_ptr(), tmask.data_ptr(), None, b * L, _lib.stream_ptr())
+    tmask = eng._e(n)
+    _lib.call("ste_mask_i64_to_f32", tmask_i64.data_ptr(), tmask.data_ptr(), None, n, _lib.stream_ptr())
     scores = ops.linear(c1, s.w(PRE + "alignment_confidence.2.weight"), s.p(PRE + "alignment_confidence.2.bias"),
                         row_scale=tmask)
-    return scores.view(b, L), matrix, emit
+    return scores.view(n)
+
+
+def hit_spans(token_spans, ntok, lead=1, trail=1):
+    """The phrase's span inside each pair's decoded path: from the first frame of token `lead` to the
+    end of token n - 1 - trail, n = ntok.  With lead = trail = 1 that is the transcript without its
+    <s> and </s>, which absorb the audio before and after the phrase.  token_spans int
+    [..., L, 2], ntok int [...] -> int32 [..., 2]; (-1, -1) when n < lead + trail + 1 or the pair has
+    no path (its spans are -1).  Pure torch, any device."""
+    if lead < 0 or trail < 0:
+        raise ValueError(f"lead and trail count tokens, got {lead}, {trail}")
+    L = token_spans.shape[-2]
+    n = ntok.to(token_spans.device, torch.int64)
+    ok = (n >= lead + trail + 1) & (n <= L)
+    first = torch.full_like(n, min(lead, L - 1)).unsqueeze(-1)
+    last = (n - 1 - trail).clamp(0, L - 1).unsqueeze(-1)
+    start = token_spans[..., 0].to(torch.int64).gather(-1, first).squeeze(-1)
+    end = token_spans[..., 1].to(torch.int64).gather(-1, last).squeeze(-1)
+    ok = ok & (start >= 0) & (end >= 0)
+    neg = torch.full_like(start, -1)
+    return torch.stack([torch.where(ok, start, neg), torch.where(ok, end, neg)], -1).to(torch.int32)
 
 
 def words_from_tokens(token_spans, token_scores, word_ids):

@@ -4,7 +4,9 @@
 //                         alignment_weights.mean(dim=1)), its frame-major log and the attention
 //                         output, one block per query group looping over all heads so that
 //                         per-head probabilities stay in LDS;
-//   ste_align_decode      the monotone (Viterbi) path through that log matrix, one wave per pair.
+//   ste_align_matrix_seg_fwd  the same block for (query, segment) pairs over runs of rows of one K/V
+//                         buffer, an AudioStateStore's alignment rows read in place;
+//   ste_align_decode     the monotone (Viterbi) path through that log matrix, one wave per pair.
 #include "common.h"
 #include "../../include/ste.h"
 
@@ -21,15 +23,23 @@ namespace {
 constexpr int NT = 1024, QB = 8, DMAX = 256, VU = 8;
 constexpr int TMAX = 2048, DEC_LMAX = 256, PF = 8;   // decode: emission rows in flight per lane
 
-// q bf16 [B*L, ldq] (head h at cols h*d), kv bf16 [B*T, ldkv] (K at h*d, V at P + h*d)
-__global__ __launch_bounds__(NT) void align_matrix_kernel(const bf16* q, int64_t ldq, const bf16* kv, int64_t ldkv,
-                                                        const int32_t* kmask, int L, int T, int P, int nh,
-                                                        float scale, float inv_nh, float* matrix, float* emit,
-                                                        int64_t lde, bf16* out, int64_t ldo) {
-  extern __shared__ float ss[];  // QB * T score rows, then QB * T running head sums
-  __shared__ float sq[QB][DMAX];
+// One block's work, shared by the dense and the segmented kernel: QB query rows from l0 of one query
+// block against T consecutive K/V rows.  The arithmetic is one text; SEG selects how the seven
+// addresses are formed.
+//   SEG = false  the dense kernel's own expressions on the whole-batch pointers, clip / transcript b:
+//                row b*L + l of q and out, row b*T + t of kv and kmask, matrix [B][L][T], emit [B][T][lde].
+//   SEG = true   every pointer is already that of the block's pair (b = 0, no mask): row l of the query
+//                block at q + l*ldq, row t of the segment at kv + t*ldkv, matrix [L][ldm], emit [T][lde],
+//                out [L][ldo].  Inside the segment an element of kv is addressed by a 32-bit offset from
+//                the (scalar) row pointer: the entry point refuses Tmax*ldkv + 2P >= 2^31.
+// ss holds QB * T score rows, then QB * T running head sums: the layout depends on T alone.
+template <bool SEG>
+STE_DEV void align_matrix_block(const bf16* q, int64_t ldq, const bf16* kv, int64_t ldkv, const int32_t* kmask, int l0,
+                                int b, int L, int T, int P, int nh, float scale, float inv_nh, float* matrix,
+                                int64_t ldm, float* emit, int64_t lde, bf16* out, int64_t ldo, float* ss,
+                                float (&sq)[QB][DMAX]) {
   float* sacc = ss + QB * T;
-  const int l0 = blockIdx.x * QB, b = blockIdx.y;
+  const int ldk = (int)ldkv;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int d = P / nh;
   const int nq = min(QB, L - l0);
@@ -41,7 +51,7 @@ __global__ __launch_bounds__(NT) void align_matrix_kernel(const bf16* q, int64_t
     }
     __syncthreads();
     for (int t = tid; t < T; t += NT) {
-      const bf16* kr = kv + (int64_t)(b * T + t) * ldkv + h * d;
+      const bf16* kr = SEG ? kv + (t * ldk + h * d) : kv + (int64_t)(b * T + t) * ldkv + h * d;
       float acc[QB];
 #pragma unroll
       for (int qi = 0; qi < QB; ++qi) acc[qi] = 0.f;
@@ -54,7 +64,7 @@ __global__ __launch_bounds__(NT) void align_matrix_kernel(const bf16* q, int64_t
           for (int qi = 0; qi < QB; ++qi) acc[qi] += kf * sq[qi][c + e];
         }
       }
-      const bool valid = kmask == nullptr || kmask[b * T + t] != 0;
+      const bool valid = SEG || kmask == nullptr || kmask[b * T + t] != 0;
 #pragma unroll
       for (int qi = 0; qi < QB; ++qi) ss[qi * T + t] = valid ? acc[qi] : -INFINITY;
     }
@@ -80,17 +90,17 @@ __global__ __launch_bounds__(NT) void align_matrix_kernel(const bf16* q, int64_t
       for (int i = tid; i < nq * d; i += NT) {
         const int qi = i / d, c = i % d;
         const float* pr = ss + qi * T;
-        const bf16* vc = kv + (int64_t)(b * T) * ldkv + P + h * d + c;
+        const bf16* vc = SEG ? kv + (P + h * d + c) : kv + (int64_t)(b * T) * ldkv + P + h * d + c;
         float acc = 0.f;
         int t = 0;
         for (; t + VU <= T; t += VU) {  // VU value rows in flight, then the same sums in the same order
           float v[VU];
 #pragma unroll
-          for (int u = 0; u < VU; ++u) v[u] = (float)vc[(int64_t)(t + u) * ldkv];
+          for (int u = 0; u < VU; ++u) v[u] = (float)(SEG ? vc[(t + u) * ldk] : vc[(int64_t)(t + u) * ldkv]);
 #pragma unroll
           for (int u = 0; u < VU; ++u) acc += pr[t + u] * v[u];
         }
-        for (; t < T; ++t) acc += pr[t] * (float)vc[(int64_t)t * ldkv];
+        for (; t < T; ++t) acc += pr[t] * (float)(SEG ? vc[t * ldk] : vc[(int64_t)t * ldkv]);
         out[(int64_t)(b * L + l0 + qi) * ldo + h * d + c] = (bf16)acc;
       }
     }
@@ -99,7 +109,7 @@ __global__ __launch_bounds__(NT) void align_matrix_kernel(const bf16* q, int64_t
   if (matrix != nullptr) {
     for (int i = tid; i < nq * T; i += NT) {
       const int qi = i / T, t = i % T;
-      matrix[((int64_t)b * L + l0 + qi) * T + t] = sacc[qi * T + t] * inv_nh;
+      matrix[((int64_t)b * L + l0 + qi) * (SEG ? ldm : (int64_t)T) + t] = sacc[qi * T + t] * inv_nh;
     }
   }
   if (emit != nullptr) {  // frame-major: the nq columns of a frame are adjacent
@@ -108,6 +118,54 @@ __global__ __launch_bounds__(NT) void align_matrix_kernel(const bf16* q, int64_t
       emit[((int64_t)b * T + t) * lde + l0 + qi] = logf(fmaxf(sacc[qi * T + t] * inv_nh, FLT_MIN));
     }
   }
+}
+
+// q bf16 [B*L, ldq], kv bf16 [B*T, ldkv]: block (x, b) owns queries QB*x .. of clip b
+__global__ __launch_bounds__(NT) void align_matrix_kernel(const bf16* q, int64_t ldq, const bf16* kv, int64_t ldkv,
+                                                        const int32_t* kmask, int L, int T, int P, int nh,
+                                                        float scale, float inv_nh, float* matrix, float* emit,
+                                                        int64_t lde, bf16* out, int64_t ldo) {
+  extern __shared__ float ss[];
+  __shared__ float sq[QB][DMAX];
+  align_matrix_block<false>(q, ldq, kv, ldkv, kmask, blockIdx.x * QB, blockIdx.y, L, T, P, nh, scale, inv_nh, matrix, T,
+                            emit, lde, out, ldo, ss, sq);
+}
+
+STE_DEV int64_t uniform64(int64_t v) {  // readfirstlane of both halves
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+  const uint32_t hi = __builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+  return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// The segmented form: block (x, y) owns queries QB*x .. of pair r = r0 + y, which is query
+// block qblk[r] of q against the F = seg_len[g] rows from seg_row[g] of kv, g = pseg[r]: the dense
+// block at T = F, with the pair's rows of matrix [R, L, Tmax], emit [R, Tmax, lde] and out [R*L, ldo].
+// An empty pair (a negative index, a segment outside [0, G), F == 0 or F > Tmax) zeroes its out
+// rows, reads no row of q or kv and leaves matrix and emit alone.  The test is uniform per block.
+__global__ __launch_bounds__(NT) void align_matrix_seg_kernel(const bf16* q, int64_t ldq, const int32_t* qblk,
+                                                            const int32_t* pseg, const bf16* kv, int64_t ldkv,
+                                                            const int64_t* seg_row, const int32_t* seg_len, int r0,
+                                                            int G, int L, int Tmax, int P, int nh, float scale,
+                                                            float inv_nh, float* matrix, float* emit, int64_t lde,
+                                                            bf16* out, int64_t ldo) {
+  extern __shared__ float ss[];
+  __shared__ float sq[QB][DMAX];
+  const int64_t r = (int64_t)r0 + blockIdx.y;
+  const int l0 = blockIdx.x * QB;
+  // the pair's table entries are the same in every lane: held in scalar registers (92 -> 63 vector registers)
+  const int u = __builtin_amdgcn_readfirstlane(qblk[r]), g = __builtin_amdgcn_readfirstlane(pseg[r]);
+  const int F = __builtin_amdgcn_readfirstlane(g >= 0 && g < G ? seg_len[g] : 0);
+  if (u < 0 || F <= 0 || F > Tmax) {
+    if (out != nullptr) {
+      const int nq = min(QB, L - l0);
+      for (int i = threadIdx.x; i < nq * P; i += NT) out[(r * L + l0 + i / P) * ldo + i % P] = (bf16)0.f;
+    }
+    return;
+  }
+  align_matrix_block<true>(q + (int64_t)u * L * ldq, ldq, kv + uniform64(seg_row[g]) * ldkv, ldkv, nullptr, l0, 0, L, F, P,
+                           nh, scale, inv_nh, matrix == nullptr ? nullptr : matrix + r * L * Tmax, Tmax,
+                           emit == nullptr ? nullptr : emit + r * Tmax * lde, lde,
+                           out == nullptr ? nullptr : out + r * L * ldo, ldo, ss, sq);
 }
 
 // ------------------------------------------------------------------ monotone decode
@@ -216,6 +274,19 @@ __global__ __launch_bounds__(64) void align_decode_kernel(const float* emit, int
   }
 }
 
+// Dynamic LDS of a matrix kernel: beyond what every device grants, ask this one and raise the
+// kernel's limit.  0, STE_ERR_SHAPE when the device cannot hold it, or the runtime's error.
+int matrix_lds(const void* kernel, size_t lds) {
+  if (lds <= 48 * 1024) return 0;
+  int dev = 0, lim = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) e = hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
+  if (e != hipSuccess) return (int)e;
+  if (lds + sizeof(float) * QB * DMAX > (size_t)lim) return STE_ERR_SHAPE;
+  e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  return e == hipSuccess ? 0 : (int)e;
+}
+
 }  // namespace
 
 extern "C" int ste_align_matrix_fwd(const void* q, int64_t ldq, const void* kv, int64_t ldkv, const int32_t* kmask,
@@ -226,20 +297,36 @@ extern "C" int ste_align_matrix_fwd(const void* q, int64_t ldq, const void* kv, 
   const int d = P / nh;
   if (d > DMAX || d % 8 || T > TMAX || B > 65535 || (emit != nullptr && lde < L)) return STE_ERR_SHAPE;
   const size_t lds = (size_t)2 * QB * T * sizeof(float);
-  if (lds > 48 * 1024) {  // beyond what every device grants: ask this one
-    int dev = 0, lim = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e == hipSuccess) e = hipDeviceGetAttribute(&lim, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
-    if (e != hipSuccess) return (int)e;
-    if (lds + sizeof(float) * QB * DMAX > (size_t)lim) return STE_ERR_SHAPE;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(align_matrix_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-  }
+  if (const int rc = matrix_lds(reinterpret_cast<const void*>(align_matrix_kernel), lds)) return rc;
   hipLaunchKernelGGL(align_matrix_kernel, dim3((L + QB - 1) / QB, B), dim3(NT), lds, (hipStream_t)stream,
                      (const bf16*)q, ldq, (const bf16*)kv, ldkv, kmask, L, T, P, nh, 1.0f / sqrtf((float)d),
                      1.0f / (float)nh, matrix, emit, lde, (bf16*)out, ldo);
   STE_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int ste_align_matrix_seg_fwd(const void* q, int64_t ldq, const int32_t* qblk, const int32_t* pseg,
+                                        const void* kv, int64_t ldkv, const int64_t* seg_row, const int32_t* seg_len,
+                                        int R, int G, int L, int Tmax, int P, int nh, float* matrix, float* emit,
+                                        int64_t lde, void* out, int64_t ldo, void* stream) {
+  if (q == nullptr || qblk == nullptr || pseg == nullptr || kv == nullptr || seg_row == nullptr || seg_len == nullptr)
+    return STE_ERR_ARG;
+  if (matrix == nullptr && emit == nullptr && out == nullptr) return STE_ERR_ARG;
+  if (R <= 0 || G <= 0 || L <= 0 || Tmax <= 0 || nh <= 0 || P <= 0 || P % nh) return STE_ERR_SHAPE;
+  const int d = P / nh;
+  if (d > DMAX || d % 8 || Tmax > TMAX) return STE_ERR_SHAPE;
+  if (ldq < P || ldkv < 2 * (int64_t)P || ldkv % 8 || (uintptr_t)kv % 16) return STE_ERR_SHAPE;  // 16-byte key loads
+  if ((int64_t)Tmax * ldkv + 2 * (int64_t)P > INT32_MAX) return STE_ERR_SHAPE;      // 32-bit offsets inside a segment
+  if ((emit != nullptr && lde < L) || (out != nullptr && ldo < P)) return STE_ERR_SHAPE;
+  const size_t lds = (size_t)2 * QB * Tmax * sizeof(float);
+  if (const int rc = matrix_lds(reinterpret_cast<const void*>(align_matrix_seg_kernel), lds)) return rc;
+  const float scale = 1.0f / sqrtf((float)d), inv_nh = 1.0f / (float)nh;
+  for (int r0 = 0; r0 < R; r0 += 65535) {  // the pair rides grid.y
+    hipLaunchKernelGGL(align_matrix_seg_kernel, dim3((L + QB - 1) / QB, min(R - r0, 65535)), dim3(NT), lds,
+                       (hipStream_t)stream, (const bf16*)q, ldq, qblk, pseg, (const bf16*)kv, ldkv, seg_row, seg_len,
+                       r0, G, L, Tmax, P, nh, scale, inv_nh, matrix, emit, lde, (bf16*)out, ldo);
+    STE_CHECK_LAUNCH();
+  }
   return 0;
 }
 

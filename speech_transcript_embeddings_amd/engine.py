@@ -1426,6 +1426,104 @@ class Engine:
             out.update(word_spans=ws, word_seconds=seconds(ws), word_scores=wsc)
         return out
 
+    @torch.no_grad()
+    def locate_clips(self, th, tmask, store, candidates, word_ids=None, lead=1, trail=1, pair_batch=128,
+                     return_matrix=False, return_emit=False):
+        """Where in each of k candidate corpus clips is a text query spoken: align_pairs for
+        (query, stored clip) pairs, without the waveforms and without an audio-encoder pass.  Text
+        hidden [Q,L,Ht] + prefix mask [Q,L] (None = every token valid); store: a
+        retrieval.AudioStateStore(align_rows=True) built with these weights (else ValueError /
+        RuntimeError); candidates int [Q,k] of clip ids in [-1, len(store)), -1 = empty slot.
+
+        The head's queries are projected once per query; pair (i, n) runs query block i over clip n's
+        stored alignment K|V rows in place (ops.align_matrix_seg_fwd, the clip ids being the segment
+        indices of the store's own table), then align.confidence_tail and ops.align_decode with ntok
+        from the query and nfrm from the clip.  The pairs run in chunks of pair_batch, which bounds
+        the emissions buffer at pair_batch·Tmax·L·4 bytes; Tmax, the longest candidate clip, comes
+        with the one device -> host sync of the argument checks.
+
+        -> dict of [Q, k, ...] tensors: token_spans int32 [Q,k,L,2] and token_seconds, scores fp32
+        [Q,k,L], path_score fp32 [Q,k], hit_spans int32 [Q,k,2] and hit_seconds (align.hit_spans:
+        first frame of token `lead` to the end of token n-1-trail), word_spans / word_seconds /
+        word_scores with word_ids int [Q,L]; matrix fp32 [Q,k,L,Tmax] / emit fp32 [Q,k,Tmax,L] on
+        request (frames past a clip's own are 0 / -inf).  An empty slot and an infeasible pair (fewer
+        frames than tokens) have spans (-1, -1), path_score -inf and scores 0."""
+        from .align import confidence_tail, hit_spans, text_queries, words_from_tokens
+        m, dev = self.m, self.s.device
+        if not m.use_word_alignment:
+            raise ValueError("locate_clips needs a model built with use_word_alignment=True")
+        if not getattr(store, "align_rows", False):
+            raise ValueError("locate_clips needs an AudioStateStore built with align_rows=True")
+        Q, L, Ht = th.shape
+        P = m.projection_dim
+        cand = candidates.to(dev, torch.int32).contiguous()
+        if cand.dim() != 2 or cand.shape[0] != Q or cand.shape[1] < 1:
+            raise ValueError(f"candidates must be [{Q}, k >= 1], got {tuple(cand.shape)}")
+        k = cand.shape[1]
+        R = Q * k
+        N = len(store)
+        tm = (torch.ones(Q, L, dtype=torch.int64, device=dev) if tmask is None
+              else tmask.to(dev, torch.int64).contiguous())
+        pseg = cand.view(-1)
+        live = (pseg >= 0) & (pseg < N)          # a clip id outside the store is refused below, never looked up
+        nfrm = (store.frames.index_select(0, torch.where(live, pseg, 0).long()) * live if N
+                else torch.zeros(R, dtype=torch.int32, device=dev)).to(torch.int32)
+        bad = (tm[:, 1:] > tm[:, :-1]).any()
+        lo, hi, bad, Tmax = (int(x) for x in torch.stack((cand.min(), cand.max(), bad.to(torch.int32),
+                                                           nfrm.max())).tolist())
+        if lo < -1 or hi >= N:
+            raise ValueError(f"candidates must lie in [-1, {N}), got [{lo}, {hi}]")
+        if bad:
+            raise ValueError("locate_clips needs prefix text masks (right-padded transcripts)")
+        store.check()
+        fs = self.frame_seconds
+
+        def seconds(sp):
+            return torch.where(sp < 0, -1.0, sp.float() * fs)
+
+        qblk = torch.where(live, torch.arange(R, device=dev, dtype=torch.int32) // k, -1).to(torch.int32)
+        ntok = ((tm != 0).sum(1, dtype=torch.int32).repeat_interleave(k) * live).to(torch.int32)
+        spans = torch.full((R, L, 2), -1, dtype=torch.int32, device=dev)
+        scores = torch.zeros(R, L, device=dev, dtype=F32)
+        path = torch.full((R,), float("-inf"), device=dev, dtype=F32)
+        Tm = max(Tmax, 1)
+        matrix = torch.zeros(R, L, Tm, device=dev, dtype=F32) if return_matrix else None
+        emit_all = torch.full((R, Tm, L), float("-inf"), device=dev, dtype=F32) if return_emit else None
+        if Tmax > 0:                            # else every slot is empty
+            nh = m.word_level_alignment.num_heads
+            thf = th.reshape(Q * L, Ht).float().contiguous()
+            q = text_queries(self, ops.cast_bf16(thf, self._e(Q * L, Ht, dtype=BF16)))      # once per query
+            seg_row, seg_len = store.seg_row, store.frames
+            step = max(int(pair_batch), 1)
+            for r0 in range(0, R, step):
+                r1 = min(r0 + step, R)
+                n = r1 - r0
+                qb, row = qblk[r0:r1].contiguous(), qblk[r0:r1].clamp(min=0).long()
+                emit = emit_all[r0:r1] if return_emit else self._e(n, Tmax, L)
+                att = self._e(n * L, P, dtype=BF16)
+                ops.align_matrix_seg_fwd(q, qb, pseg[r0:r1].contiguous(), store.akv, seg_row, seg_len, L, Tmax, nh,
+                                         matrix=None if matrix is None else matrix[r0:r1], emit=emit, out=att)
+                th_rows = thf.view(Q, L, Ht).index_select(0, row).view(n * L, Ht)
+                tm_rows = (tm.index_select(0, row) * (qb >= 0).view(n, 1)).contiguous()
+                scores[r0:r1] = confidence_tail(self, att, th_rows, tm_rows, n * L).view(n, L)
+                spans[r0:r1], path[r0:r1] = ops.align_decode(emit, ntok[r0:r1].contiguous(),
+                                                             nfrm[r0:r1].contiguous())
+        hits = hit_spans(spans, ntok, lead, trail)
+        out = dict(token_spans=spans.view(Q, k, L, 2), token_seconds=seconds(spans).view(Q, k, L, 2),
+                   scores=scores.view(Q, k, L), path_score=path.view(Q, k), hit_spans=hits.view(Q, k, 2),
+                   hit_seconds=seconds(hits).view(Q, k, 2))
+        if return_matrix:
+            out["matrix"] = matrix.view(Q, k, L, Tm)
+        if return_emit:
+            out["emit"] = emit_all.view(Q, k, Tm, L)
+        if word_ids is not None:
+            wid = word_ids.to(dev).repeat_interleave(k, 0)
+            ws, wsc = words_from_tokens(spans, scores, wid)
+            W = ws.shape[1]
+            out.update(word_spans=ws.view(Q, k, W, 2), word_seconds=seconds(ws).view(Q, k, W, 2),
+                       word_scores=wsc.view(Q, k, W))
+        return out
+
     # ============================================================== full step
     def forward(self, batch, train: bool, save: bool = True):
         """compute_pos_neg_embeddings (ref:502-565) -> (tp_fused, tn_fused, a_fused, align, ctx).

@@ -357,6 +357,38 @@ class EnhancedAudioTextModel(nn.Module):
         self.store.sync_shadow()
         return self.engine.align_pairs(th, attention_mask, ah, attention_mask_audio, word_ids, return_matrix)
 
+    @torch.no_grad()
+    def locate_clips(self, input_ids, attention_mask, store, candidates, *, word_ids=None, text_encoded=None,
+                     lead=1, trail=1, pair_batch=128, return_matrix=False, return_emit=False):
+        """align() for search hits: where in each of k candidate corpus clips is text
+        query i spoken.  store: a retrieval.AudioStateStore(align_rows=True) built from this model with
+        its present weights; candidates int [Q, k] are clip ids of the store (-1 = empty), as returned
+        by store.search or rerank_clips.  One text-encoder pass per query, no audio pass and no
+        waveform: the clips' alignment rows are read from the store (Engine.locate_clips).  Needs
+        use_word_alignment and a prefix text mask, else ValueError.  text_encoded: the (projection,
+        hidden) pair of an encode_text call already made on these transcripts in eval mode, to skip
+        the text pass.  Forward only, inference arithmetic (the training flag is forced off and
+        restored).
+
+        Returns a dict of [Q, k, ...] tensors: align()'s token_spans / token_seconds / scores /
+        path_score (and word_* with word_ids int [Q, L]) per (query, clip) pair, plus hit_spans int32
+        [Q, k, 2] / hit_seconds: the first frame of token `lead` to the end of token n - 1 - trail,
+        i.e. the phrase without its <s> / </s>, (-1, -1) when the transcript has fewer than
+        lead + trail + 1 tokens.  An empty slot, and a clip with fewer frames than the query has
+        tokens, give (-1, -1) spans and path_score -inf."""
+        if not self.use_word_alignment:
+            raise ValueError("locate_clips() needs a model built with use_word_alignment=True")
+        if attention_mask is None:
+            attention_mask = torch.ones_like(input_ids)
+        was_training, self.training = self.training, False   # encode_text reads the flag: no dropout here
+        try:
+            _, th = text_encoded or self.encode_text(input_ids, attention_mask)
+        finally:
+            self.training = was_training
+        self.store.sync_shadow()
+        return self.engine.locate_clips(th, attention_mask, store, candidates, word_ids, lead, trail, pair_batch,
+                                        return_matrix, return_emit)
+
     def _encode_nograd(self, kind, x, mask):
         self.store.sync_shadow()
         e = self.engine

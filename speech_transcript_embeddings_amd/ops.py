@@ -791,6 +791,29 @@ def align_matrix_fwd(q, kv, kmask, B, L, T, nh, *, matrix=None, emit=None, out=N
          0 if emit is None else emit.stride(1), ptr(out), 0 if out is None else _ld(out), _s())
 
 
+def align_matrix_seg_fwd(q, qblk, pseg, kv, seg_row, seg_len, L, Tmax, nh, *, matrix=None, emit=None, out=None):
+    """align_matrix_fwd for R (query, segment) pairs over runs of rows of one K|V buffer
+    (ste_align_matrix_seg_fwd): q bf16 [U*L, ldq], qblk / pseg int32 [R] (the pair's query
+    block and segment, negative = empty pair), kv bf16 [rows, 2P] (an AudioStateStore's akv, read in
+    place), seg_row int64 [G] / seg_len int32 [G], Tmax >= every pair's segment length.  Any of matrix
+    fp32 [R, L, Tmax], emit fp32 [R, Tmax, lde >= L] and out bf16 [R*L, ldo]; a pair with F frames
+    writes rows [:F] only, the bits of align_matrix_fwd(B = 1, T = F) on its rows."""
+    R, G = qblk.numel(), seg_row.numel()
+    P = kv.shape[-1] // 2
+    assert q.dtype == BF16 and kv.dtype == BF16 and q.dim() == 2 and kv.dim() == 2 and q.stride(1) == 1
+    assert kv.stride(1) == 1
+    assert qblk.dtype == torch.int32 and pseg.dtype == torch.int32 and pseg.numel() == R
+    assert qblk.is_contiguous() and pseg.is_contiguous() and seg_row.is_contiguous() and seg_len.is_contiguous()
+    assert seg_row.dtype == torch.int64 and seg_len.dtype == torch.int32 and seg_len.numel() == G
+    assert matrix is None or (matrix.dtype == F32 and matrix.is_contiguous() and matrix.numel() == R * L * Tmax)
+    assert emit is None or (emit.dtype == F32 and emit.shape[:2] == (R, Tmax) and emit.stride(2) == 1
+                            and emit.stride(0) == Tmax * emit.stride(1))
+    assert out is None or (out.dtype == BF16 and out.shape[0] >= R * L and out.stride(1) == 1)
+    call("ste_align_matrix_seg_fwd", ptr(q), _ld(q), ptr(qblk), ptr(pseg), ptr(kv), _ld(kv), ptr(seg_row), ptr(seg_len),
+         R, G, int(L), int(Tmax), P, int(nh), ptr(matrix), ptr(emit), 0 if emit is None else emit.stride(1), ptr(out),
+         0 if out is None else _ld(out), _s())
+
+
 def align_decode(emit, ntok, nfrm):
     """Monotone (Viterbi) decode of frame-major emissions (ste_align_decode): emit fp32 [B, T, L]
     (a column view of a wider [B, T, lde] buffer is fine), ntok / nfrm int32 [B] -> (spans int32

@@ -30,6 +30,9 @@ of every clip; they are computed once when the corpus is indexed and attended ov
     plan_clip_pairs(idx)                          -> the (query, clip) pairs grouped by clip, in tiles
     rerank_clips(model, input_ids, attention_mask, store, idx) -> (values, indices)
     evaluate_retrieval(..., rerank_k=k, rerank_t2a=True) -> also "t2a_rerank"
+    AudioStateStore(model, align_rows=True): also the alignment head's K|V rows (DESIGN §20);
+        align_kv_rows(n), align_bytes_per_frame(dim)
+    search_clips(model, store, input_ids, attention_mask, k) -> (values, indices, where in each hit)
 
 Scores and selection run in ste_topk_sim (csrc/retrieval.hip): the queries x corpus score matrix
 is never written.  The order is total (value descending, index ascending) and a row's score is
@@ -252,6 +255,16 @@ def kv_bytes_per_frame(dim: int, kv_dtype: str = "bf16") -> int:
     raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
 
 
+ALIGN_MAX_FRAMES = 2048   # the T limit of ste_align_matrix_seg_fwd and ste_align_decode
+
+
+def align_bytes_per_frame(dim: int) -> int:
+    """Bytes an AudioStateStore(align_rows=True) of projection width dim adds per stored frame: one
+    bf16 K|V row of the alignment head, 2·dim columns = 4·dim bytes (3,072 at dim = 768), whatever
+    kv_dtype is."""
+    return 4 * dim
+
+
 class AudioStateStore:
     """What the text -> audio fused pair score needs of every corpus clip, computed once when the
     corpus is indexed: the clip's projection aproj fp32 [P], its unit row (in an
@@ -271,12 +284,19 @@ class AudioStateStore:
               its bf16 rows alone.  Needs P % 64 == 0, else ValueError.
     kv_rows(n) says what clip n's stored rows mean, as bf16, for either.
 
+    align_rows=True (needs use_word_alignment, else ValueError) also keeps the word-alignment head's
+    bf16 K|V rows of the same valid frames in akv [capacity, 2P], row for row beside kv:
+    seg_row and frames address both, and ste_align_matrix_seg_fwd reads them in place
+    (model.locate_clips).  4P more bytes per frame (align_bytes_per_frame), bf16 under either
+    kv_dtype; a clip of more than 2048 valid frames is a ValueError in add.  align_kv_rows(n) gives
+    clip n's rows.
+
     The store is valid for the weights it was built with: it records the model's
     ParamStore.weights_token() at the first add, and adding to or scoring against it after the
     weights changed raises RuntimeError (check)."""
 
     def __init__(self, model, device="cuda", index_dtype: torch.dtype = F32, reserve_frames: int = 0,
-                 kv_dtype: str = "bf16"):
+                 kv_dtype: str = "bf16", align_rows: bool = False):
         self.model, self.device = model, torch.device(device)
         self.dim = int(model.projection_dim)
         self.fused = bool(getattr(model, "use_cross_modal", False))
@@ -286,13 +306,19 @@ class AudioStateStore:
             raise ValueError(f'kv_dtype="mx8" needs projection_dim % 64 == 0 (MX blocks of 32 over the 2P columns, '
                              f"quantised 128 at a time), got {self.dim}")
         self.kv_dtype = kv_dtype
+        self.align_rows = bool(align_rows)
+        if self.align_rows and not getattr(model, "use_word_alignment", False):
+            raise ValueError("align_rows=True needs a model built with use_word_alignment=True")
         self.index = EmbeddingIndex(self.dim, index_dtype, self.device)
         cap = max(int(reserve_frames), 0) if self.fused else 0
         mx8 = kv_dtype == "mx8"
         self.kv = torch.empty(cap, 2 * self.dim, device=self.device, dtype=torch.uint8 if mx8 else BF16)
         # the E8M0 block scales of kv's rows (mx8 only): grown together with kv
         self.kv_scales = torch.empty(cap, 2 * self.dim // 32, device=self.device, dtype=torch.uint8) if mx8 else None
-        self.rows = 0                         # rows of kv in use
+        # the alignment head's K|V rows (align_rows only), numbered as kv's rows are
+        self.akv = torch.empty(max(int(reserve_frames), 0), 2 * self.dim, device=self.device, dtype=BF16) \
+            if self.align_rows else None
+        self.rows = 0                         # rows of kv / akv in use
         self._seg_row: list[int] = []
         self._seg_len: list[int] = []
         self._aproj: list[torch.Tensor] = []
@@ -307,8 +333,17 @@ class AudioStateStore:
         if self._token is not None and self._token != self.model.store.weights_token():
             raise RuntimeError("the AudioStateStore was built with other weights: rebuild it after a weight update")
 
+    def _reserve_align(self, rows: int) -> None:
+        if rows <= self.akv.shape[0]:
+            return
+        grown = torch.empty(max(rows, 2 * self.akv.shape[0]), self.akv.shape[1], device=self.device, dtype=BF16)
+        grown[:self.rows].copy_(self.akv[:self.rows])
+        self.akv = grown
+
     def _reserve(self, rows: int) -> None:
-        if rows <= self.kv.shape[0]:
+        if self.align_rows:
+            self._reserve_align(rows)
+        if not self.fused or rows <= self.kv.shape[0]:
             return
         cap = max(rows, 2 * self.kv.shape[0])
         grown = torch.empty(cap, self.kv.shape[1], device=self.device, dtype=self.kv.dtype)
@@ -348,14 +383,22 @@ class AudioStateStore:
             *frames, bad = torch.cat([fm.sum(1), bad.view(1).to(torch.int64)]).tolist()
             if bad:
                 raise ValueError("AudioStateStore.add needs prefix audio masks with at least one valid frame per clip")
-        if self.fused:
+        if self.align_rows and max(frames) > ALIGN_MAX_FRAMES:
+            raise ValueError(f"align_rows=True holds clips of at most {ALIGN_MAX_FRAMES} valid frames "
+                             f"(the alignment kernels' limit), got {max(frames)}")
+        if self.fused or self.align_rows:
             model.store.sync_shadow()
             ahb = ops.cast_bf16(ah.reshape(B * T, Ha).float().contiguous(),
                                 torch.empty(B * T, Ha, device=self.device, dtype=BF16))
-            kv = eng._kv("text_to_audio_attention", "audio_seq_to_projection", ahb)[0]
             self._reserve(self.rows + sum(frames))
-            # (source, destination): the bf16 rows, or their e4m3 bytes and E8M0 scales
-            pairs = [(kv, self.kv)] if self.kv_scales is None else list(zip(ops.mx8_quant(kv), (self.kv, self.kv_scales)))
+            pairs = []   # (source, destination): the bf16 rows, or their e4m3 bytes and E8M0 scales
+            if self.fused:
+                kv = eng._kv("text_to_audio_attention", "audio_seq_to_projection", ahb)[0]
+                pairs = [(kv, self.kv)] if self.kv_scales is None \
+                    else list(zip(ops.mx8_quant(kv), (self.kv, self.kv_scales)))
+            if self.align_rows:
+                from .align import audio_kv
+                pairs.append((audio_kv(eng, ahb), self.akv))
             for src, dst in pairs:
                 if all(n == T for n in frames):
                     dst[self.rows:self.rows + B * T].copy_(src)
@@ -403,7 +446,8 @@ class AudioStateStore:
         """Bytes held for the clips added so far (the K/V rows in use, aproj, the unit rows and the segment table)."""
         n = len(self)
         return (self.rows * kv_bytes_per_frame(self.dim, self.kv_dtype) + n * self.dim * 4
-                + n * self.dim * (2 if self.index.dtype == BF16 else 4) + n * 12)
+                + n * self.dim * (2 if self.index.dtype == BF16 else 4) + n * 12
+                + (self.rows * align_bytes_per_frame(self.dim) if self.align_rows else 0))
 
     def kv_rows(self, n: int) -> torch.Tensor:
         """Clip n's stored K|V rows as bf16 [frames, 2P]: a slice of kv for "bf16" (a view), what the
@@ -415,6 +459,13 @@ class AudioStateStore:
         if self.kv_scales is None:
             return self.kv[a:b]
         return ops.mx8_dequant(self.kv[a:b], self.kv_scales[a:b])
+
+    def align_kv_rows(self, n: int) -> torch.Tensor:
+        """Clip n's stored alignment-head K|V rows, bf16 [frames, 2P] (a view of akv)."""
+        if not self.align_rows:
+            raise ValueError("the store keeps no alignment rows without align_rows=True")
+        a = self._seg_row[n]
+        return self.akv[a:a + self._seg_len[n]]
 
     def search(self, text_emb: torch.Tensor, k: int):
         """Stage 1: (values fp32 [Q, k], indices int32 [Q, k]) of the k best clips per unit text row,
@@ -429,6 +480,29 @@ def rerank_clips(model, input_ids, attention_mask, store, idx, *, text_encoded=N
     Returns (values fp32 [Q, k], indices [Q, k]).  text_encoded: see score_clips."""
     scores = model.score_clips(input_ids, attention_mask, store, idx, text_encoded=text_encoded)
     return rerank_order(scores, torch.as_tensor(idx).to(scores.device))
+
+
+@torch.no_grad()
+def search_clips(model, store, input_ids, attention_mask, k, *, rerank=True, locate=True, word_ids=None):
+    """A typed phrase against an indexed archive, end to end: ONE text-encoder pass per
+    query, shared by store.search (stage 1), rerank_clips (stage 2, with rerank=True and a
+    use_cross_modal model) and model.locate_clips (where in each hit the phrase is spoken, with
+    locate=True; needs a store built with align_rows=True).  Returns (values fp32 [Q, k], indices
+    [Q, k], location): the hits in their final (reranked) order and model.locate_clips' dict for
+    exactly those indices, None with locate=False."""
+    if attention_mask is None:
+        attention_mask = torch.ones_like(input_ids)
+    was_training, model.training = model.training, False   # encode_text reads the flag: no dropout here
+    try:
+        enc = model.encode_text(input_ids, attention_mask)
+    finally:
+        model.training = was_training
+    vals, idx = store.search(_unit_rows(enc[0]), k)
+    if rerank and getattr(model, "use_cross_modal", False):
+        vals, idx = rerank_clips(model, input_ids, attention_mask, store, idx, text_encoded=enc)
+    where = model.locate_clips(input_ids, attention_mask, store, idx, word_ids=word_ids, text_encoded=enc) \
+        if locate else None
+    return vals, idx, where
 
 
 def _pad_rows(chunks, fill):

@@ -30,6 +30,8 @@ through them); the fused training step itself calls the C ABI directly (engine.p
         ste::xattn_seg on rows stored as MX-fp8 bytes and E8M0 block scales (DESIGN §19)
     ste::align_matrix(q, kv, kmask?, nh) -> (matrix, emit, out)
         WordLevelAlignmentModule's head-averaged alignment_matrix (ref :295), its frame-major log, the output
+    ste::align_matrix_seg(q, qblk, pseg, kv, seg_row, seg_len, Tmax, nh) -> (matrix, emit, out)
+        ste::align_matrix for (text query, stored corpus clip) pairs: segments of one K|V buffer (DESIGN §20)
     ste::align_decode(emit, ntok, nfrm) -> (spans, score)
         monotone (Viterbi) decode of that log matrix into one frame span per token
 
@@ -383,6 +385,39 @@ def _align_matrix_fake(q, kv, kmask, nh):
     return (q.new_empty(B, L, T, dtype=F32), q.new_empty(B, T, L, dtype=F32), q.new_empty(B, L, P, dtype=BF16))
 
 
+@torch.library.custom_op("ste::align_matrix_seg", mutates_args=())
+def align_matrix_seg(q: Tensor, qblk: Tensor, pseg: Tensor, kv: Tensor, seg_row: Tensor, seg_len: Tensor, Tmax: int,
+                     nh: int) -> tuple[Tensor, Tensor, Tensor]:
+    """ste::align_matrix for R (query, segment) pairs over runs of rows of one K|V buffer (forward only):
+    q [U, L, P], qblk / pseg int [R] (query block and segment of a pair, negative = empty pair), kv
+    [rows, 2P] (bf16, or fp32 cast to bf16), seg_row int64 [G] / seg_len int [G] (first row and length
+    of a segment), Tmax >= the pairs' segment lengths -> (matrix fp32 [R, L, Tmax], emit fp32
+    [R, Tmax, L], out bf16 [R, L, P]).  A pair with F frames fills frames [:F]; the frames beyond,
+    and an empty pair's, are 0 in matrix and -inf in emit."""
+    U, L, P = q.shape
+    R, Tmax = qblk.numel(), int(Tmax)
+    if kv.dim() != 2 or kv.shape[1] != 2 * P:
+        raise ValueError(f"align_matrix_seg: q {tuple(q.shape)}, kv {tuple(kv.shape)}")
+    matrix = torch.zeros(R, L, Tmax, device=q.device, dtype=F32)
+    emit = torch.full((R, Tmax, L), float("-inf"), device=q.device, dtype=F32)
+    out = torch.empty(R * L, P, device=q.device, dtype=BF16)
+
+    def i32(t):
+        return t.reshape(-1).to(torch.int32).contiguous()
+
+    ops.align_matrix_seg_fwd(_bf16(q.reshape(U * L, P)), i32(qblk), i32(pseg), _bf16(kv),
+                             seg_row.reshape(-1).to(torch.int64).contiguous(), i32(seg_len), L, Tmax, int(nh),
+                             matrix=matrix, emit=emit, out=out)
+    return matrix, emit, out.view(R, L, P)
+
+
+@align_matrix_seg.register_fake
+def _align_matrix_seg_fake(q, qblk, pseg, kv, seg_row, seg_len, Tmax, nh):
+    _, L, P = q.shape
+    R = qblk.numel()
+    return (q.new_empty(R, L, Tmax, dtype=F32), q.new_empty(R, Tmax, L, dtype=F32), q.new_empty(R, L, P, dtype=BF16))
+
+
 @torch.library.custom_op("ste::align_decode", mutates_args=())
 def align_decode(emit: Tensor, ntok: Tensor, nfrm: Tensor) -> tuple[Tensor, Tensor]:
     """Monotone (Viterbi) path through emit fp32 [B, T, L] (frame-major log alignment) for ntok[b]
@@ -399,4 +434,4 @@ def _align_decode_fake(emit, ntok, nfrm):
 
 
 OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim", "xattn_mq",
-       "xattn_seg", "xattn_seg_mx8", "align_matrix", "align_decode")
+       "xattn_seg", "xattn_seg_mx8", "align_matrix", "align_matrix_seg", "align_decode")
