@@ -564,6 +564,20 @@ int ste_align_matrix_seg_fwd(const void* q, int64_t ldq, const int32_t* qblk, co
                              int64_t ldkv, const int64_t* seg_row, const int32_t* seg_len, int R, int G, int L,
                              int Tmax, int P, int nh, float* matrix, float* emit, int64_t lde, void* out, int64_t ldo,
                              void* stream);
+/* ste_align_matrix_seg_fwd on MX-fp8 rows.  kv is a [rows][ldkv] buffer of OCP e4m3 bytes
+ * = [K | V] (ldkv in bytes, >= 2P), scales the [rows][lds] buffer of their E8M0 block scales: the scale of
+ * column c (0 <= c < 2P) of a row is scales[row*lds + c/32] (an AudioStateStore's akv / akv_scales:
+ * ldkv = 2P, lds = 2P/32).  An element is read as bf16(float(e4m3) * 2^(E - 127)) (ste_mx8_dequant) and
+ * from there on the arithmetic is ste_align_matrix_seg_fwd's: for every pair, rows [:F] of matrix, emit
+ * and out are bit-identical to that kernel on the dequantised rows; empty pairs, frames >= F and
+ * padding columns behave as there.  The shape rule of ste_align_matrix_seg_fwd with P % 32 == 0,
+ * ldkv % 8 == 0, kv 8-B aligned, lds >= 2P/32, Tmax·ldkv + 2P < 2^31 and Tmax·lds + 2P/32 < 2^31;
+ * otherwise STE_ERR_SHAPE.  A NULL q, qblk, pseg, kv, scales, seg_row or seg_len, or no requested
+ * output, is STE_ERR_ARG.  All of these come before any launch.  No atomics, no workspace. */
+int ste_align_matrix_seg_mx8_fwd(const void* q, int64_t ldq, const int32_t* qblk, const int32_t* pseg, const void* kv,
+                                 int64_t ldkv, const void* scales, int64_t lds, const int64_t* seg_row,
+                                 const int32_t* seg_len, int R, int G, int L, int Tmax, int P, int nh, float* matrix,
+                                 float* emit, int64_t lde, void* out, int64_t ldo, void* stream);
 /* Monotone (Viterbi) decode of frame-major emissions emit fp32 [B, T, lde] into one frame span per
  * token.  Pair b has tokens 0..n-1 (n = ntok[b]) and frames 0..F-1 (F = nfrm[b]); the path l(t)
  * maximises Σ_t emit[b][t][l(t)] under l(0) = 0, l(F-1) = n-1, l(t) - l(t-1) in {0, 1}.  The

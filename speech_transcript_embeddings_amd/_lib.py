@@ -210,6 +210,9 @@ _SIGS = {
     "ste_align_matrix_seg_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p,
                                          c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64,
                                          c_void_p, c_int64, c_void_p]),
+    "ste_align_matrix_seg_mx8_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                             c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int,
+                                             c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "ste_align_decode": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p]),
     "ste_rank1_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,

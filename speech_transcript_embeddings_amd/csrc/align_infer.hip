@@ -6,6 +6,8 @@
 //                         per-head probabilities stay in LDS;
 //   ste_align_matrix_seg_fwd  the same block for (query, segment) pairs over runs of rows of one K/V
 //                         buffer, an AudioStateStore's alignment rows read in place;
+//   ste_align_matrix_seg_mx8_fwd  the same on rows stored as MX-fp8 (e4m3 bytes + one E8M0 scale per
+//                         32 columns): the bits of the bf16 kernel on the dequantised rows;
 //   ste_align_decode     the monotone (Viterbi) path through that log matrix, one wave per pair.
 #include "common.h"
 #include "../../include/ste.h"
@@ -22,6 +24,27 @@ namespace {
 // order, depend on neither.
 constexpr int NT = 1024, QB = 8, DMAX = 256, VU = 8;
 constexpr int TMAX = 2048, DEC_LMAX = 256, PF = 8;   // decode: emission rows in flight per lane
+// MX: key fragments loaded together in the score loop; queries per thread (of QB) and value rows in
+// flight in the out loop.  Out loop at Q = 64, k = 10, P = 768, 4 heads, T = 500 / 1500, one launch of 640
+// pairs: MXQ = 2, MXU = 16: 4.28 / 13.1 ms; 8, 32: 5.68 / 16.2; 4, 16: 13.0 / 38.4; 4, 32:
+// 12.0 / 35.1 (the bf16 kernel: 5.46 / 16.5).  MXK = 1 -> 4: the kernel without out 1.57 -> 1.35 / 9.45 -> 4.54.
+constexpr int MXK = 4;
+constexpr int MXQ = 2;
+constexpr int MXU = 16;
+static_assert(QB % MXQ == 0, "a group's queries are split evenly over the threads of a column");
+
+template <bool MX> struct kv_elem { typedef bf16 type; };
+template <> struct kv_elem<true> { typedef uint8_t type; };
+
+// 8 key columns from c of one row against the QB scaled query rows: 64 FMAs, column by column
+STE_DEV void score_fragment(float (&acc)[QB], bf16x8 kk, const float (&sq)[QB][DMAX], int c) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const float kf = (float)kk[e];
+#pragma unroll
+    for (int qi = 0; qi < QB; ++qi) acc[qi] += kf * sq[qi][c + e];
+  }
+}
 
 // One block's work, shared by the dense and the segmented kernel: QB query rows from l0 of one query
 // block against T consecutive K/V rows.  The arithmetic is one text; SEG selects how the seven
@@ -33,11 +56,22 @@ constexpr int TMAX = 2048, DEC_LMAX = 256, PF = 8;   // decode: emission rows in
 //                out [L][ldo].  Inside the segment an element of kv is addressed by a 32-bit offset from
 //                the (scalar) row pointer: the entry point refuses Tmax*ldkv + 2P >= 2^31.
 // ss holds QB * T score rows, then QB * T running head sums: the layout depends on T alone.
-template <bool SEG>
-STE_DEV void align_matrix_block(const bf16* q, int64_t ldq, const bf16* kv, int64_t ldkv, const int32_t* kmask, int l0,
-                                int b, int L, int T, int P, int nh, float scale, float inv_nh, float* matrix,
-                                int64_t ldm, float* emit, int64_t lde, bf16* out, int64_t ldo, float* ss,
-                                float (&sq)[QB][DMAX]) {
+//   MX (with SEG)  kv is e4m3 bytes (ldkv in bytes) and sc row 0 of the segment's E8M0 scales, row stride
+//                lsc bytes, one scale per 32 columns of [K | V].  The code differs where an
+//                element enters a register and nowhere else: a key fragment comes through mx8_dequant8
+//                as the bf16x8 the bf16 code loads, a value element through mx8_dequant1 as the bf16 it
+//                loads.  The out loop gives a thread one value column and MXQ queries of the group
+//                (one byte and one scale byte per value row, MXU rows in flight, dequantised once and
+//                used MXQ times) where the bf16 code gives it one column of one query: an output
+//                element is still one fp32 sum of p_t * v_t in ascending t, so its bits are the same
+//                whichever thread holds it.
+template <bool SEG, bool MX = false>
+STE_DEV void align_matrix_block(const bf16* q, int64_t ldq, const typename kv_elem<MX>::type* kv, int64_t ldkv,
+                                const uint8_t* sc, int lsc, const int32_t* kmask, int l0, int b, int L, int T, int P,
+                                int nh, float scale, float inv_nh, float* matrix, int64_t ldm, float* emit,
+                                int64_t lde, bf16* out, int64_t ldo, float* ss, float (&sq)[QB][DMAX]) {
+  static_assert(SEG || !MX, "MX rows are read by the segmented kernel only");
+  typedef typename kv_elem<MX>::type kv_t;
   float* sacc = ss + QB * T;
   const int ldk = (int)ldkv;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -51,18 +85,31 @@ STE_DEV void align_matrix_block(const bf16* q, int64_t ldq, const bf16* kv, int6
     }
     __syncthreads();
     for (int t = tid; t < T; t += NT) {
-      const bf16* kr = SEG ? kv + (t * ldk + h * d) : kv + (int64_t)(b * T + t) * ldkv + h * d;
+      const kv_t* kr = SEG ? kv + (t * ldk + h * d) : kv + (int64_t)(b * T + t) * ldkv + h * d;
       float acc[QB];
 #pragma unroll
       for (int qi = 0; qi < QB; ++qi) acc[qi] = 0.f;
-      for (int c = 0; c < d; c += 8) {
-        const bf16x8 kk = *reinterpret_cast<const bf16x8*>(kr + c);
+      if constexpr (MX) {
+        // MXK fragments (32 columns) are loaded together, then used in the same order: a lane's
+        // fragments share a cache line, and between two fragments' 64 FMAs the other waves' rows
+        // would evict it (the bf16 code makes half as many loads for the same columns)
+        for (int c0 = 0; c0 < d; c0 += 8 * MXK) {
+          uint2 raw[MXK];
+          uint32_t E[MXK];
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float kf = (float)kk[e];
+          for (int j = 0; j < MXK; ++j) {
+            if (c0 + 8 * j < d) {
+              raw[j] = *reinterpret_cast<const uint2*>(kr + c0 + 8 * j);
+              E[j] = sc[t * lsc + ((h * d + c0 + 8 * j) >> 5)];
+            }
+          }
 #pragma unroll
-          for (int qi = 0; qi < QB; ++qi) acc[qi] += kf * sq[qi][c + e];
+          for (int j = 0; j < MXK; ++j) {
+            if (c0 + 8 * j < d) score_fragment(acc, mx8_dequant8(raw[j], E[j]), sq, c0 + 8 * j);
+          }
         }
+      } else {
+        for (int c = 0; c < d; c += 8) score_fragment(acc, *reinterpret_cast<const bf16x8*>(kr + c), sq, c);
       }
       const bool valid = SEG || kmask == nullptr || kmask[b * T + t] != 0;
 #pragma unroll
@@ -86,11 +133,47 @@ STE_DEV void align_matrix_block(const bf16* q, int64_t ldq, const bf16* kv, int6
       }
     }
     __syncthreads();
-    if (out != nullptr) {
+    if constexpr (MX) {
+      if (out != nullptr) {
+        for (int i = tid; i < (QB / MXQ) * d; i += NT) {
+          const int q0 = (i / d) * MXQ, c = i % d;  // queries q0 .. q0 + MXQ - 1, value column c of the head
+          if (q0 >= nq) continue;
+          const float* pr = ss + q0 * T;
+          // kv and sc are uniform (scalar) bases: an element is one 32-bit offset from them
+          const uint32_t vcol = P + h * d + c, scol = vcol >> 5;
+          float acc[MXQ];  // rows qi >= nq of ss hold the zero queries' scores: summed, never stored
+#pragma unroll
+          for (int qi = 0; qi < MXQ; ++qi) acc[qi] = 0.f;
+          int t = 0;
+          for (; t + MXU <= T; t += MXU) {  // MXU value rows in flight, then the same sums in the same order
+            uint32_t v[MXU], E[MXU];
+#pragma unroll
+            for (int u = 0; u < MXU; ++u) {
+              v[u] = kv[(uint32_t)((t + u) * ldk) + vcol];
+              E[u] = sc[(uint32_t)((t + u) * lsc) + scol];
+            }
+#pragma unroll
+            for (int u = 0; u < MXU; ++u) {
+              const float vf = (float)mx8_dequant1(v[u], E[u]);
+#pragma unroll
+              for (int qi = 0; qi < MXQ; ++qi) acc[qi] += pr[qi * T + t + u] * vf;
+            }
+          }
+          for (; t < T; ++t) {
+            const float vf = (float)mx8_dequant1(kv[(uint32_t)(t * ldk) + vcol], sc[(uint32_t)(t * lsc) + scol]);
+#pragma unroll
+            for (int qi = 0; qi < MXQ; ++qi) acc[qi] += pr[qi * T + t] * vf;
+          }
+#pragma unroll
+          for (int qi = 0; qi < MXQ; ++qi)
+            if (q0 + qi < nq) out[(int64_t)(b * L + l0 + q0 + qi) * ldo + h * d + c] = (bf16)acc[qi];
+        }
+      }
+    } else if (out != nullptr) {
       for (int i = tid; i < nq * d; i += NT) {
         const int qi = i / d, c = i % d;
         const float* pr = ss + qi * T;
-        const bf16* vc = SEG ? kv + (P + h * d + c) : kv + (int64_t)(b * T) * ldkv + P + h * d + c;
+        const kv_t* vc = SEG ? kv + (P + h * d + c) : kv + (int64_t)(b * T) * ldkv + P + h * d + c;
         float acc = 0.f;
         int t = 0;
         for (; t + VU <= T; t += VU) {  // VU value rows in flight, then the same sums in the same order
@@ -127,8 +210,8 @@ __global__ __launch_bounds__(NT) void align_matrix_kernel(const bf16* q, int64_t
                                                         int64_t lde, bf16* out, int64_t ldo) {
   extern __shared__ float ss[];
   __shared__ float sq[QB][DMAX];
-  align_matrix_block<false>(q, ldq, kv, ldkv, kmask, blockIdx.x * QB, blockIdx.y, L, T, P, nh, scale, inv_nh, matrix, T,
-                            emit, lde, out, ldo, ss, sq);
+  align_matrix_block<false>(q, ldq, kv, ldkv, nullptr, 0, kmask, blockIdx.x * QB, blockIdx.y, L, T, P, nh, scale,
+                            inv_nh, matrix, T, emit, lde, out, ldo, ss, sq);
 }
 
 STE_DEV int64_t uniform64(int64_t v) {  // readfirstlane of both halves
@@ -142,8 +225,11 @@ STE_DEV int64_t uniform64(int64_t v) {  // readfirstlane of both halves
 // block at T = F, with the pair's rows of matrix [R, L, Tmax], emit [R, Tmax, lde] and out [R*L, ldo].
 // An empty pair (a negative index, a segment outside [0, G), F == 0 or F > Tmax) zeroes its out
 // rows, reads no row of q or kv and leaves matrix and emit alone.  The test is uniform per block.
+// MX: kv is the buffer of e4m3 bytes and sc that of its rows' E8M0 scales, row stride lsc (else NULL, 0).
+template <bool MX>
 __global__ __launch_bounds__(NT) void align_matrix_seg_kernel(const bf16* q, int64_t ldq, const int32_t* qblk,
-                                                            const int32_t* pseg, const bf16* kv, int64_t ldkv,
+                                                            const int32_t* pseg, const typename kv_elem<MX>::type* kv,
+                                                            int64_t ldkv, const uint8_t* sc, int64_t lsc,
                                                             const int64_t* seg_row, const int32_t* seg_len, int r0,
                                                             int G, int L, int Tmax, int P, int nh, float scale,
                                                             float inv_nh, float* matrix, float* emit, int64_t lde,
@@ -162,10 +248,12 @@ __global__ __launch_bounds__(NT) void align_matrix_seg_kernel(const bf16* q, int
     }
     return;
   }
-  align_matrix_block<true>(q + (int64_t)u * L * ldq, ldq, kv + uniform64(seg_row[g]) * ldkv, ldkv, nullptr, l0, 0, L, F, P,
-                           nh, scale, inv_nh, matrix == nullptr ? nullptr : matrix + r * L * Tmax, Tmax,
-                           emit == nullptr ? nullptr : emit + r * Tmax * lde, lde,
-                           out == nullptr ? nullptr : out + r * L * ldo, ldo, ss, sq);
+  const int64_t row0 = uniform64(seg_row[g]);
+  align_matrix_block<true, MX>(q + (int64_t)u * L * ldq, ldq, kv + row0 * ldkv, ldkv, MX ? sc + row0 * lsc : nullptr,
+                               (int)lsc, nullptr, l0, 0, L, F, P, nh, scale, inv_nh,
+                               matrix == nullptr ? nullptr : matrix + r * L * Tmax, Tmax,
+                               emit == nullptr ? nullptr : emit + r * Tmax * lde, lde,
+                               out == nullptr ? nullptr : out + r * L * ldo, ldo, ss, sq);
 }
 
 // ------------------------------------------------------------------ monotone decode
@@ -305,29 +393,56 @@ extern "C" int ste_align_matrix_fwd(const void* q, int64_t ldq, const void* kv, 
   return 0;
 }
 
-extern "C" int ste_align_matrix_seg_fwd(const void* q, int64_t ldq, const int32_t* qblk, const int32_t* pseg,
-                                        const void* kv, int64_t ldkv, const int64_t* seg_row, const int32_t* seg_len,
-                                        int R, int G, int L, int Tmax, int P, int nh, float* matrix, float* emit,
-                                        int64_t lde, void* out, int64_t ldo, void* stream) {
-  if (q == nullptr || qblk == nullptr || pseg == nullptr || kv == nullptr || seg_row == nullptr || seg_len == nullptr)
+namespace {
+// the checks and launches shared by ste_align_matrix_seg_fwd (MX = false) and ste_align_matrix_seg_mx8_fwd
+// (sc / lsc: the E8M0 scales and their row stride)
+template <bool MX>
+int align_matrix_seg_launch(const void* q, int64_t ldq, const int32_t* qblk, const int32_t* pseg, const void* kv,
+                            int64_t ldkv, const void* sc, int64_t lsc, const int64_t* seg_row, const int32_t* seg_len,
+                            int R, int G, int L, int Tmax, int P, int nh, float* matrix, float* emit, int64_t lde,
+                            void* out, int64_t ldo, void* stream) {
+  if (q == nullptr || qblk == nullptr || pseg == nullptr || kv == nullptr || seg_row == nullptr || seg_len == nullptr ||
+      (MX && sc == nullptr))
     return STE_ERR_ARG;
   if (matrix == nullptr && emit == nullptr && out == nullptr) return STE_ERR_ARG;
   if (R <= 0 || G <= 0 || L <= 0 || Tmax <= 0 || nh <= 0 || P <= 0 || P % nh) return STE_ERR_SHAPE;
   const int d = P / nh;
   if (d > DMAX || d % 8 || Tmax > TMAX) return STE_ERR_SHAPE;
-  if (ldq < P || ldkv < 2 * (int64_t)P || ldkv % 8 || (uintptr_t)kv % 16) return STE_ERR_SHAPE;  // 16-byte key loads
+  // 16-byte key loads of bf16, 8-byte ones of e4m3
+  if (ldq < P || ldkv < 2 * (int64_t)P || ldkv % 8 || (uintptr_t)kv % (MX ? 8 : 16)) return STE_ERR_SHAPE;
+  if (MX && (P % 32 || lsc < 2 * (int64_t)P / 32)) return STE_ERR_SHAPE;             // whole 32-column scale blocks
   if ((int64_t)Tmax * ldkv + 2 * (int64_t)P > INT32_MAX) return STE_ERR_SHAPE;      // 32-bit offsets inside a segment
+  if (MX && (int64_t)Tmax * lsc + 2 * (int64_t)P / 32 > INT32_MAX) return STE_ERR_SHAPE;
   if ((emit != nullptr && lde < L) || (out != nullptr && ldo < P)) return STE_ERR_SHAPE;
+  typedef typename kv_elem<MX>::type kv_t;
   const size_t lds = (size_t)2 * QB * Tmax * sizeof(float);
-  if (const int rc = matrix_lds(reinterpret_cast<const void*>(align_matrix_seg_kernel), lds)) return rc;
+  if (const int rc = matrix_lds(reinterpret_cast<const void*>(align_matrix_seg_kernel<MX>), lds)) return rc;
   const float scale = 1.0f / sqrtf((float)d), inv_nh = 1.0f / (float)nh;
   for (int r0 = 0; r0 < R; r0 += 65535) {  // the pair rides grid.y
-    hipLaunchKernelGGL(align_matrix_seg_kernel, dim3((L + QB - 1) / QB, min(R - r0, 65535)), dim3(NT), lds,
-                       (hipStream_t)stream, (const bf16*)q, ldq, qblk, pseg, (const bf16*)kv, ldkv, seg_row, seg_len,
-                       r0, G, L, Tmax, P, nh, scale, inv_nh, matrix, emit, lde, (bf16*)out, ldo);
+    hipLaunchKernelGGL(align_matrix_seg_kernel<MX>, dim3((L + QB - 1) / QB, min(R - r0, 65535)), dim3(NT), lds,
+                       (hipStream_t)stream, (const bf16*)q, ldq, qblk, pseg, (const kv_t*)kv, ldkv, (const uint8_t*)sc,
+                       lsc, seg_row, seg_len, r0, G, L, Tmax, P, nh, scale, inv_nh, matrix, emit, lde, (bf16*)out, ldo);
     STE_CHECK_LAUNCH();
   }
   return 0;
+}
+}  // namespace
+
+extern "C" int ste_align_matrix_seg_fwd(const void* q, int64_t ldq, const int32_t* qblk, const int32_t* pseg,
+                                        const void* kv, int64_t ldkv, const int64_t* seg_row, const int32_t* seg_len,
+                                        int R, int G, int L, int Tmax, int P, int nh, float* matrix, float* emit,
+                                        int64_t lde, void* out, int64_t ldo, void* stream) {
+  return align_matrix_seg_launch<false>(q, ldq, qblk, pseg, kv, ldkv, nullptr, 0, seg_row, seg_len, R, G, L, Tmax, P, nh,
+                                        matrix, emit, lde, out, ldo, stream);
+}
+
+extern "C" int ste_align_matrix_seg_mx8_fwd(const void* q, int64_t ldq, const int32_t* qblk, const int32_t* pseg,
+                                            const void* kv, int64_t ldkv, const void* scales, int64_t lds,
+                                            const int64_t* seg_row, const int32_t* seg_len, int R, int G, int L,
+                                            int Tmax, int P, int nh, float* matrix, float* emit, int64_t lde, void* out,
+                                            int64_t ldo, void* stream) {
+  return align_matrix_seg_launch<true>(q, ldq, qblk, pseg, kv, ldkv, scales, lds, seg_row, seg_len, R, G, L, Tmax, P, nh,
+                                       matrix, emit, lde, out, ldo, stream);
 }
 
 extern "C" int ste_align_decode(const float* emit, int64_t lde, const int32_t* ntok, const int32_t* nfrm, int B,

@@ -112,6 +112,14 @@ STE_DEV bf16x8 mx8_dequant8(uint2 b, uint32_t E) {
   r[4] = (bf16)(f2[0] * s), r[5] = (bf16)(f2[1] * s), r[6] = (bf16)(f3[0] * s), r[7] = (bf16)(f3[1] * s);
   return r;
 }
+// One element of the same: the e4m3 byte b (bits 7..0 of the register).  Each step is mx8_dequant8's
+// for that element: the fp8 -> fp32 conversion is exact packed or single, the scale comes from the same
+// integer rule, the product is one v_mul_f32 and the rounding the same fp32 -> bf16 conversion, so the
+// bits are that element's of mx8_dequant8, the rounded bf16 subnormals included.
+STE_DEV bf16 mx8_dequant1(uint32_t b, uint32_t E) {
+  const float s = __builtin_bit_cast(float, E == 0u ? 0x00400000u : E == 255u ? 0x7fc00000u : E << 23);
+  return (bf16)(__builtin_amdgcn_cvt_f32_fp8((int)b, 0) * s);
+}
 STE_DEV float sigmoidf_(float x) { return 1.0f / (1.0f + __expf(-x)); }
 STE_DEV float swish_f(float x) { return x * sigmoidf_(x); }
 STE_DEV float swish_d(float x) {

@@ -1436,8 +1436,9 @@ class Engine:
         RuntimeError); candidates int [Q,k] of clip ids in [-1, len(store)), -1 = empty slot.
 
         The head's queries are projected once per query; pair (i, n) runs query block i over clip n's
-        stored alignment K|V rows in place (ops.align_matrix_seg_fwd, the clip ids being the segment
-        indices of the store's own table), then align.confidence_tail and ops.align_decode with ntok
+        stored alignment K|V rows in place (ops.align_matrix_seg_fwd, or ops.align_matrix_seg_mx8_fwd on
+        a store built with align_dtype="mx8"; the clip ids being the segment indices of the store's
+        own table), then align.confidence_tail and ops.align_decode with ntok
         from the query and nfrm from the clip.  The pairs run in chunks of pair_batch, which bounds
         the emissions buffer at pair_batch·Tmax·L·4 bytes; Tmax, the longest candidate clip, comes
         with the one device -> host sync of the argument checks.
@@ -1501,8 +1502,13 @@ class Engine:
                 qb, row = qblk[r0:r1].contiguous(), qblk[r0:r1].clamp(min=0).long()
                 emit = emit_all[r0:r1] if return_emit else self._e(n, Tmax, L)
                 att = self._e(n * L, P, dtype=BF16)
-                ops.align_matrix_seg_fwd(q, qb, pseg[r0:r1].contiguous(), store.akv, seg_row, seg_len, L, Tmax, nh,
-                                         matrix=None if matrix is None else matrix[r0:r1], emit=emit, out=att)
+                outs = dict(matrix=None if matrix is None else matrix[r0:r1], emit=emit, out=att)
+                if getattr(store, "align_dtype", "bf16") == "mx8":   # e4m3 bytes + E8M0 scales, read in place (§21)
+                    ops.align_matrix_seg_mx8_fwd(q, qb, pseg[r0:r1].contiguous(), store.akv, store.akv_scales, seg_row,
+                                                 seg_len, L, Tmax, nh, **outs)
+                else:
+                    ops.align_matrix_seg_fwd(q, qb, pseg[r0:r1].contiguous(), store.akv, seg_row, seg_len, L, Tmax,
+                                             nh, **outs)
                 th_rows = thf.view(Q, L, Ht).index_select(0, row).view(n * L, Ht)
                 tm_rows = (tm.index_select(0, row) * (qb >= 0).view(n, 1)).contiguous()
                 scores[r0:r1] = confidence_tail(self, att, th_rows, tm_rows, n * L).view(n, L)

@@ -814,6 +814,30 @@ def align_matrix_seg_fwd(q, qblk, pseg, kv, seg_row, seg_len, L, Tmax, nh, *, ma
          0 if out is None else _ld(out), _s())
 
 
+def align_matrix_seg_mx8_fwd(q, qblk, pseg, kv, scales, seg_row, seg_len, L, Tmax, nh, *, matrix=None, emit=None,
+                             out=None):
+    """align_matrix_seg_fwd on MX-fp8 rows (ste_align_matrix_seg_mx8_fwd): kv uint8 [rows, 2P]
+    of e4m3 bytes and scales uint8 [rows, 2P/32] of their E8M0 block scales (an AudioStateStore's akv /
+    akv_scales, read in place; row-strided views are fine).  The other operands and the outputs as
+    align_matrix_seg_fwd; the same bits as that on mx8_dequant(kv, scales)."""
+    R, G = qblk.numel(), seg_row.numel()
+    P = kv.shape[-1] // 2
+    assert q.dtype == BF16 and q.dim() == 2 and q.stride(1) == 1
+    assert kv.dtype == torch.uint8 and kv.dim() == 2 and kv.stride(1) == 1
+    assert scales.dtype == torch.uint8 and scales.dim() == 2 and scales.stride(1) == 1
+    assert scales.shape[0] == kv.shape[0] and scales.shape[1] * 32 == kv.shape[1]
+    assert qblk.dtype == torch.int32 and pseg.dtype == torch.int32 and pseg.numel() == R
+    assert qblk.is_contiguous() and pseg.is_contiguous() and seg_row.is_contiguous() and seg_len.is_contiguous()
+    assert seg_row.dtype == torch.int64 and seg_len.dtype == torch.int32 and seg_len.numel() == G
+    assert matrix is None or (matrix.dtype == F32 and matrix.is_contiguous() and matrix.numel() == R * L * Tmax)
+    assert emit is None or (emit.dtype == F32 and emit.shape[:2] == (R, Tmax) and emit.stride(2) == 1
+                            and emit.stride(0) == Tmax * emit.stride(1))
+    assert out is None or (out.dtype == BF16 and out.shape[0] >= R * L and out.stride(1) == 1)
+    call("ste_align_matrix_seg_mx8_fwd", ptr(q), _ld(q), ptr(qblk), ptr(pseg), ptr(kv), _ld(kv), ptr(scales),
+         _ld(scales), ptr(seg_row), ptr(seg_len), R, G, int(L), int(Tmax), P, int(nh), ptr(matrix), ptr(emit),
+         0 if emit is None else emit.stride(1), ptr(out), 0 if out is None else _ld(out), _s())
+
+
 def align_decode(emit, ntok, nfrm):
     """Monotone (Viterbi) decode of frame-major emissions (ste_align_decode): emit fp32 [B, T, L]
     (a column view of a wider [B, T, lde] buffer is fine), ntok / nfrm int32 [B] -> (spans int32

@@ -258,11 +258,15 @@ def kv_bytes_per_frame(dim: int, kv_dtype: str = "bf16") -> int:
 ALIGN_MAX_FRAMES = 2048   # the T limit of ste_align_matrix_seg_fwd and ste_align_decode
 
 
-def align_bytes_per_frame(dim: int) -> int:
-    """Bytes an AudioStateStore(align_rows=True) of projection width dim adds per stored frame: one
-    bf16 K|V row of the alignment head, 2·dim columns = 4·dim bytes (3,072 at dim = 768), whatever
-    kv_dtype is."""
-    return 4 * dim
+def align_bytes_per_frame(dim: int, align_dtype: str = "bf16") -> int:
+    """Bytes an AudioStateStore(align_rows=True) of projection width dim adds per stored frame, whatever
+    kv_dtype is: one K|V row of the alignment head, 2·dim columns.  "bf16" 4·dim bytes (3,072 at
+    dim = 768); "mx8" 2·dim e4m3 bytes + 2·dim/32 E8M0 scale bytes (1,584 at dim = 768)."""
+    if align_dtype == "bf16":
+        return 4 * dim
+    if align_dtype == "mx8":
+        return 2 * dim + 2 * dim // 32
+    raise ValueError(f"align_dtype must be one of {KV_DTYPES}, got {align_dtype!r}")
 
 
 class AudioStateStore:
@@ -287,16 +291,22 @@ class AudioStateStore:
     align_rows=True (needs use_word_alignment, else ValueError) also keeps the word-alignment head's
     bf16 K|V rows of the same valid frames in akv [capacity, 2P], row for row beside kv:
     seg_row and frames address both, and ste_align_matrix_seg_fwd reads them in place
-    (model.locate_clips).  4P more bytes per frame (align_bytes_per_frame), bf16 under either
-    kv_dtype; a clip of more than 2048 valid frames is a ValueError in add.  align_kv_rows(n) gives
-    clip n's rows.
+    (model.locate_clips).  A clip of more than 2048 valid frames is a ValueError in add.  align_dtype
+    selects how these rows are held, independently of kv_dtype (align_bytes_per_frame):
+      "bf16"  akv bf16 [capacity, 2P]: 4P more bytes per frame (the default);
+      "mx8"   akv uint8 [capacity, 2P] of e4m3 bytes + akv_scales uint8 [capacity, 2P/32] of E8M0 block
+              scales, ops.mx8_quant of each bf16 row as it is added: 2P + P/16 more bytes per frame;
+              ste_align_matrix_seg_mx8_fwd reads the bytes in place.  Needs P % 64 == 0, else
+              ValueError.
+    Without align_rows the argument has no effect.  align_kv_rows(n) says what clip n's stored rows
+    mean, as bf16, for either.
 
     The store is valid for the weights it was built with: it records the model's
     ParamStore.weights_token() at the first add, and adding to or scoring against it after the
     weights changed raises RuntimeError (check)."""
 
     def __init__(self, model, device="cuda", index_dtype: torch.dtype = F32, reserve_frames: int = 0,
-                 kv_dtype: str = "bf16", align_rows: bool = False):
+                 kv_dtype: str = "bf16", align_rows: bool = False, align_dtype: str = "bf16"):
         self.model, self.device = model, torch.device(device)
         self.dim = int(model.projection_dim)
         self.fused = bool(getattr(model, "use_cross_modal", False))
@@ -309,6 +319,12 @@ class AudioStateStore:
         self.align_rows = bool(align_rows)
         if self.align_rows and not getattr(model, "use_word_alignment", False):
             raise ValueError("align_rows=True needs a model built with use_word_alignment=True")
+        if align_dtype not in KV_DTYPES:
+            raise ValueError(f"align_dtype must be one of {KV_DTYPES}, got {align_dtype!r}")
+        if align_dtype == "mx8" and self.align_rows and self.dim % 64:
+            raise ValueError(f'align_dtype="mx8" needs projection_dim % 64 == 0 (MX blocks of 32 over the 2P '
+                             f"columns, quantised 128 at a time), got {self.dim}")
+        self.align_dtype = align_dtype
         self.index = EmbeddingIndex(self.dim, index_dtype, self.device)
         cap = max(int(reserve_frames), 0) if self.fused else 0
         mx8 = kv_dtype == "mx8"
@@ -316,8 +332,12 @@ class AudioStateStore:
         # the E8M0 block scales of kv's rows (mx8 only): grown together with kv
         self.kv_scales = torch.empty(cap, 2 * self.dim // 32, device=self.device, dtype=torch.uint8) if mx8 else None
         # the alignment head's K|V rows (align_rows only), numbered as kv's rows are
-        self.akv = torch.empty(max(int(reserve_frames), 0), 2 * self.dim, device=self.device, dtype=BF16) \
+        amx8 = self.align_rows and align_dtype == "mx8"
+        acap = max(int(reserve_frames), 0)
+        self.akv = torch.empty(acap, 2 * self.dim, device=self.device, dtype=torch.uint8 if amx8 else BF16) \
             if self.align_rows else None
+        # the E8M0 block scales of akv's rows (align_dtype "mx8" only): grown together with akv
+        self.akv_scales = torch.empty(acap, 2 * self.dim // 32, device=self.device, dtype=torch.uint8) if amx8 else None
         self.rows = 0                         # rows of kv / akv in use
         self._seg_row: list[int] = []
         self._seg_len: list[int] = []
@@ -336,9 +356,14 @@ class AudioStateStore:
     def _reserve_align(self, rows: int) -> None:
         if rows <= self.akv.shape[0]:
             return
-        grown = torch.empty(max(rows, 2 * self.akv.shape[0]), self.akv.shape[1], device=self.device, dtype=BF16)
+        cap = max(rows, 2 * self.akv.shape[0])
+        grown = torch.empty(cap, self.akv.shape[1], device=self.device, dtype=self.akv.dtype)
         grown[:self.rows].copy_(self.akv[:self.rows])
         self.akv = grown
+        if self.akv_scales is not None:
+            grown = torch.empty(cap, self.akv_scales.shape[1], device=self.device, dtype=torch.uint8)
+            grown[:self.rows].copy_(self.akv_scales[:self.rows])
+            self.akv_scales = grown
 
     def _reserve(self, rows: int) -> None:
         if self.align_rows:
@@ -398,7 +423,9 @@ class AudioStateStore:
                     else list(zip(ops.mx8_quant(kv), (self.kv, self.kv_scales)))
             if self.align_rows:
                 from .align import audio_kv
-                pairs.append((audio_kv(eng, ahb), self.akv))
+                akv = audio_kv(eng, ahb)
+                pairs += [(akv, self.akv)] if self.akv_scales is None \
+                    else list(zip(ops.mx8_quant(akv), (self.akv, self.akv_scales)))
             for src, dst in pairs:
                 if all(n == T for n in frames):
                     dst[self.rows:self.rows + B * T].copy_(src)
@@ -447,7 +474,7 @@ class AudioStateStore:
         n = len(self)
         return (self.rows * kv_bytes_per_frame(self.dim, self.kv_dtype) + n * self.dim * 4
                 + n * self.dim * (2 if self.index.dtype == BF16 else 4) + n * 12
-                + (self.rows * align_bytes_per_frame(self.dim) if self.align_rows else 0))
+                + (self.rows * align_bytes_per_frame(self.dim, self.align_dtype) if self.align_rows else 0))
 
     def kv_rows(self, n: int) -> torch.Tensor:
         """Clip n's stored K|V rows as bf16 [frames, 2P]: a slice of kv for "bf16" (a view), what the
@@ -461,11 +488,15 @@ class AudioStateStore:
         return ops.mx8_dequant(self.kv[a:b], self.kv_scales[a:b])
 
     def align_kv_rows(self, n: int) -> torch.Tensor:
-        """Clip n's stored alignment-head K|V rows, bf16 [frames, 2P] (a view of akv)."""
+        """Clip n's stored alignment-head K|V rows as bf16 [frames, 2P]: a slice of akv for "bf16" (a
+        view), what the stored bytes mean (ops.mx8_dequant) for "mx8"."""
         if not self.align_rows:
             raise ValueError("the store keeps no alignment rows without align_rows=True")
         a = self._seg_row[n]
-        return self.akv[a:a + self._seg_len[n]]
+        b = a + self._seg_len[n]
+        if self.akv_scales is None:
+            return self.akv[a:b]
+        return ops.mx8_dequant(self.akv[a:b], self.akv_scales[a:b])
 
     def search(self, text_emb: torch.Tensor, k: int):
         """Stage 1: (values fp32 [Q, k], indices int32 [Q, k]) of the k best clips per unit text row,

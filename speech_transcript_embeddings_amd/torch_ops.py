@@ -32,6 +32,8 @@ through them); the fused training step itself calls the C ABI directly (engine.p
         WordLevelAlignmentModule's head-averaged alignment_matrix (ref :295), its frame-major log, the output
     ste::align_matrix_seg(q, qblk, pseg, kv, seg_row, seg_len, Tmax, nh) -> (matrix, emit, out)
         ste::align_matrix for (text query, stored corpus clip) pairs: segments of one K|V buffer (DESIGN §20)
+    ste::align_matrix_seg_mx8(q, qblk, pseg, kv, scales, seg_row, seg_len, Tmax, nh) -> (matrix, emit, out)
+        ste::align_matrix_seg on rows stored as MX-fp8 bytes and E8M0 block scales (DESIGN §21)
     ste::align_decode(emit, ntok, nfrm) -> (spans, score)
         monotone (Viterbi) decode of that log matrix into one frame span per token
 
@@ -418,6 +420,39 @@ def _align_matrix_seg_fake(q, qblk, pseg, kv, seg_row, seg_len, Tmax, nh):
     return (q.new_empty(R, L, Tmax, dtype=F32), q.new_empty(R, Tmax, L, dtype=F32), q.new_empty(R, L, P, dtype=BF16))
 
 
+@torch.library.custom_op("ste::align_matrix_seg_mx8", mutates_args=())
+def align_matrix_seg_mx8(q: Tensor, qblk: Tensor, pseg: Tensor, kv: Tensor, scales: Tensor, seg_row: Tensor,
+                         seg_len: Tensor, Tmax: int, nh: int) -> tuple[Tensor, Tensor, Tensor]:
+    """ste::align_matrix_seg on MX-fp8 rows (forward only): kv uint8 [rows, 2P] (OCP e4m3 bytes), scales uint8
+    [rows, 2P/32] (their E8M0 block scales); the other operands and (matrix, emit, out) as
+    ste::align_matrix_seg.  The same bits as ste::align_matrix_seg on the dequantised rows
+    (ops.mx8_dequant)."""
+    U, L, P = q.shape
+    R, Tmax = qblk.numel(), int(Tmax)
+    if (kv.dim() != 2 or kv.shape[1] != 2 * P or kv.dtype != torch.uint8 or scales.dtype != torch.uint8
+            or scales.shape != (kv.shape[0], 2 * P // 32)):
+        raise ValueError(f"align_matrix_seg_mx8: q {tuple(q.shape)}, kv {tuple(kv.shape)} {kv.dtype}, "
+                         f"scales {tuple(scales.shape)} {scales.dtype}")
+    matrix = torch.zeros(R, L, Tmax, device=q.device, dtype=F32)
+    emit = torch.full((R, Tmax, L), float("-inf"), device=q.device, dtype=F32)
+    out = torch.empty(R * L, P, device=q.device, dtype=BF16)
+
+    def i32(t):
+        return t.reshape(-1).to(torch.int32).contiguous()
+
+    ops.align_matrix_seg_mx8_fwd(_bf16(q.reshape(U * L, P)), i32(qblk), i32(pseg), kv, scales,
+                                 seg_row.reshape(-1).to(torch.int64).contiguous(), i32(seg_len), L, Tmax, int(nh),
+                                 matrix=matrix, emit=emit, out=out)
+    return matrix, emit, out.view(R, L, P)
+
+
+@align_matrix_seg_mx8.register_fake
+def _align_matrix_seg_mx8_fake(q, qblk, pseg, kv, scales, seg_row, seg_len, Tmax, nh):
+    _, L, P = q.shape
+    R = qblk.numel()
+    return (q.new_empty(R, L, Tmax, dtype=F32), q.new_empty(R, Tmax, L, dtype=F32), q.new_empty(R, L, P, dtype=BF16))
+
+
 @torch.library.custom_op("ste::align_decode", mutates_args=())
 def align_decode(emit: Tensor, ntok: Tensor, nfrm: Tensor) -> tuple[Tensor, Tensor]:
     """Monotone (Viterbi) path through emit fp32 [B, T, L] (frame-major log alignment) for ntok[b]
@@ -434,4 +469,4 @@ def _align_decode_fake(emit, ntok, nfrm):
 
 
 OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim", "xattn_mq",
-       "xattn_seg", "xattn_seg_mx8", "align_matrix", "align_matrix_seg", "align_decode")
+       "xattn_seg", "xattn_seg_mx8", "align_matrix", "align_matrix_seg", "align_matrix_seg_mx8", "align_decode")
