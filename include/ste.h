@@ -594,6 +594,31 @@ int ste_align_matrix_seg_mx8_fwd(const void* q, int64_t ldq, const int32_t* qblk
  * are assumed free of NaN and +inf (-inf is allowed). */
 int ste_align_decode(const float* emit, int64_t lde, const int32_t* ntok, const int32_t* nfrm, int B, int L, int T,
                      int32_t* spans, float* score, void* stream);
+/* Free-endpoint decode of the same emissions (phrase spotting): where inside pair b's F =
+ * nfrm[b] frames do the m = ntok[b] phrase tokens of columns lead .. lead+m-1 explain the audio better
+ * than a background of bg[b] (fp32 [B], finite) per frame.  Both ends are free: the frames before and
+ * after the hit cost nothing, a frame inside it gains g[t][j] = emit[b][t][lead+j] - bg[b] (one fp32
+ * subtract), and the hit maximises the summed gain over every (start, end, monotone path through all m
+ * tokens).  The arithmetic is fixed, for t = 0..F-1 from D_{-1} = -inf everywhere:
+ *   left_j = (j == 0 ? +0.0f : D_{t-1}[j-1]);  adv[t][j] = left_j > D_{t-1}[j]  (strict: a tie stays);
+ *   D_t[j] = (adv[t][j] ? left_j : D_{t-1}[j]) + g[t][j]   (one fp32 add; an advance of token 0 means
+ *   "the hit starts at this frame");
+ *   the end: from best = -inf, t_best = -1, after step t a D_t[m-1] > best (strict, so the earliest
+ *   frame that attains the maximum wins) becomes best, and t becomes t_best.
+ * The walk back starts at (t, j) = (t_best, m-1) with start[m] = t_best + 1: start[j] = t; on adv[t][j]
+ * j goes down (the walk ends below token 0); t goes down.  spans int32 [B, L, 2]: row lead+j =
+ * (start[j], start[j+1]), every other row (-1, -1); hit int32 [B, 2] = (start[0], t_best + 1); score
+ * fp32 [B] = best, the summed gain over the hit: a log-likelihood ratio against the background, <= 0
+ * saying that nowhere in the clip does the phrase beat it.  A pair with m < 1, lead + m > L, F < m or
+ * F > T is infeasible: spans and hit all (-1, -1), score -inf, no error; so is a pair in which no
+ * D_t[m-1] exceeds -inf (emissions of -inf only).  Frames >= F are never read.  One wave per pair, no
+ * workspace, no atomics: a pair's result does not depend on B or on the other pairs.  L <= 256,
+ * T <= 2048, lde >= L, B > 0, 0 <= lead < L, else STE_ERR_SHAPE; a NULL pointer is STE_ERR_ARG; both
+ * before a launch.  Columns outside lead .. lead+m-1 never affect the result (columns up to L-1, and
+ * with 16-byte rows up to three beyond, are read along).  The phrase's columns are assumed free of NaN
+ * and +inf, and bg finite: otherwise the result is unspecified, but every access stays in bounds. */
+int ste_align_spot(const float* emit, int64_t lde, const int32_t* ntok, const int32_t* nfrm, const float* bg,
+                   int lead, int B, int L, int T, int32_t* spans, int32_t* hit, float* score, void* stream);
 
 /* ------------------------------------------------------------------- loss --
  * F.normalize(p=2, dim=1, eps=1e-12) rows (ref:training/trainer_unfreeze.py:561-563). */

@@ -215,6 +215,8 @@ _SIGS = {
                                              c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p]),
     "ste_align_decode": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                  c_void_p]),
+    "ste_align_spot": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
     "ste_rank1_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                               c_void_p]),
     "ste_l2norm_fwd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),

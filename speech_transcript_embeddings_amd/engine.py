@@ -1377,14 +1377,33 @@ class Engine:
         return samples / SAMPLE_RATE
 
     @torch.no_grad()
-    def align_pairs(self, th, tmask, ah, amask, word_ids=None, return_matrix=False):
+    def _spot(self, emit, ntok, nfrm, lead, trail, spot_bias):
+        """The free-endpoint decode of pairs' emissions: ops.align_spot over the phrase tokens
+        lead .. n-1-trail of each pair (n = ntok; a pair with no frame, or with n - lead - trail < 1, is
+        infeasible) against bg = -log(nfrm) + spot_bias in fp32 on the device: the head's rows sum to 1
+        over a clip's frames, so at spot_bias = 0 a frame gains exactly when its token attends to it
+        more than uniformly.  -> (spans int32 [R, L, 2], hit int32 [R, 2], score fp32 [R])."""
+        if lead < 0 or trail < 0:
+            raise ValueError(f"lead and trail count tokens, got {lead}, {trail}")
+        L = emit.shape[2]
+        if lead >= L:      # no phrase column is left: every pair is infeasible, and the kernel refuses such a lead
+            lead, m = 0, torch.zeros_like(ntok)
+        else:
+            m = (ntok - (lead + trail)).clamp(min=0).to(torch.int32)
+        bg = -torch.log(nfrm.clamp(min=1).to(F32)) + float(spot_bias)
+        return ops.align_spot(emit, m.contiguous(), nfrm, bg.contiguous(), lead)
+
+    @torch.no_grad()
+    def align_pairs(self, th, tmask, ah, amask, word_ids=None, return_matrix=False, *, free_ends=False, lead=1,
+                    trail=1, spot_bias=0.0):
         """Word timestamps from the alignment head: clip b against transcript b, text
         hidden [B,L,Ht] + mask [B,L], audio hidden [B,T,Ha] + mask (frames, or wav2vec2 samples; None
         = every frame valid).  align_infer gives the confidence, the head-mean alignment matrix and its
         frame-major log; ops.align_decode turns that into one frame span per token over the pair's
         ntok = Σ text mask tokens and nfrm = Σ frame mask frames.  Both masks must be prefix masks
-        (checked on the device, one sync).  Inference arithmetic, nothing saved.  -> dict, see
-        EnhancedAudioTextModel.align."""
+        (checked on the device, one sync).  Inference arithmetic, nothing saved.  free_ends=True
+        decodes the same emissions with ops.align_spot instead (_spot; lead, trail and
+        spot_bias are read in this mode only).  -> dict, see EnhancedAudioTextModel.align."""
         from .align import align_infer, words_from_tokens
         dev = self.s.device
         B, L, Ht = th.shape
@@ -1412,13 +1431,18 @@ class Engine:
         ahb = ops.cast_bf16(ah.reshape(B * T, Ha).float().contiguous(), self._e(B * T, Ha, dtype=BF16))
         scores, matrix, emit = align_infer(self, thf, thb, ahb, B, L, T, {"a_mask32": am32, "_tmask_i64": tm},
                                            want_matrix=return_matrix, want_emit=True)
-        spans, path = ops.align_decode(emit, ntok, nfrm)
         fs = self.frame_seconds
 
         def seconds(sp):
             return torch.where(sp < 0, -1.0, sp.float() * fs)
 
+        if free_ends:
+            spans, hits, path = self._spot(emit, ntok, nfrm, lead, trail, spot_bias)
+        else:
+            spans, path = ops.align_decode(emit, ntok, nfrm)
         out = dict(token_spans=spans, token_seconds=seconds(spans), scores=scores, path_score=path)
+        if free_ends:
+            out.update(hit_spans=hits, hit_seconds=seconds(hits))
         if return_matrix:
             out["matrix"] = matrix
         if word_ids is not None:
@@ -1428,7 +1452,7 @@ class Engine:
 
     @torch.no_grad()
     def locate_clips(self, th, tmask, store, candidates, word_ids=None, lead=1, trail=1, pair_batch=128,
-                     return_matrix=False, return_emit=False):
+                     return_matrix=False, return_emit=False, *, free_ends=False, spot_bias=0.0):
         """Where in each of k candidate corpus clips is a text query spoken: align_pairs for
         (query, stored clip) pairs, without the waveforms and without an audio-encoder pass.  Text
         hidden [Q,L,Ht] + prefix mask [Q,L] (None = every token valid); store: a
@@ -1448,7 +1472,14 @@ class Engine:
         first frame of token `lead` to the end of token n-1-trail), word_spans / word_seconds /
         word_scores with word_ids int [Q,L]; matrix fp32 [Q,k,L,Tmax] / emit fp32 [Q,k,Tmax,L] on
         request (frames past a clip's own are 0 / -inf).  An empty slot and an infeasible pair (fewer
-        frames than tokens) have spans (-1, -1), path_score -inf and scores 0."""
+        frames than tokens) have spans (-1, -1), path_score -inf and scores 0.
+
+        free_ends=True replaces the decode alone: ops.align_spot over the phrase tokens
+        lead .. n-1-trail against the background -log(nfrm) + spot_bias (_spot), for a typed phrase
+        that is a fragment of what the clip says.  token_spans then hold the phrase tokens' spans and
+        (-1, -1) on the lead / trail tokens and the padding, hit_spans the kernel's hit, and path_score the
+        summed gain over the hit (a log-likelihood ratio; <= 0: the phrase nowhere beats the
+        background); scores, matrix and emit are the default mode's bits."""
         from .align import confidence_tail, hit_spans, text_queries, words_from_tokens
         m, dev = self.m, self.s.device
         if not m.use_word_alignment:
@@ -1487,6 +1518,7 @@ class Engine:
         spans = torch.full((R, L, 2), -1, dtype=torch.int32, device=dev)
         scores = torch.zeros(R, L, device=dev, dtype=F32)
         path = torch.full((R,), float("-inf"), device=dev, dtype=F32)
+        hits = torch.full((R, 2), -1, dtype=torch.int32, device=dev) if free_ends else None
         Tm = max(Tmax, 1)
         matrix = torch.zeros(R, L, Tm, device=dev, dtype=F32) if return_matrix else None
         emit_all = torch.full((R, Tm, L), float("-inf"), device=dev, dtype=F32) if return_emit else None
@@ -1512,9 +1544,14 @@ class Engine:
                 th_rows = thf.view(Q, L, Ht).index_select(0, row).view(n * L, Ht)
                 tm_rows = (tm.index_select(0, row) * (qb >= 0).view(n, 1)).contiguous()
                 scores[r0:r1] = confidence_tail(self, att, th_rows, tm_rows, n * L).view(n, L)
-                spans[r0:r1], path[r0:r1] = ops.align_decode(emit, ntok[r0:r1].contiguous(),
-                                                             nfrm[r0:r1].contiguous())
-        hits = hit_spans(spans, ntok, lead, trail)
+                if free_ends:
+                    spans[r0:r1], hits[r0:r1], path[r0:r1] = self._spot(emit, ntok[r0:r1], nfrm[r0:r1].contiguous(),
+                                                                        lead, trail, spot_bias)
+                else:
+                    spans[r0:r1], path[r0:r1] = ops.align_decode(emit, ntok[r0:r1].contiguous(),
+                                                                 nfrm[r0:r1].contiguous())
+        if not free_ends:
+            hits = hit_spans(spans, ntok, lead, trail)
         out = dict(token_spans=spans.view(Q, k, L, 2), token_seconds=seconds(spans).view(Q, k, L, 2),
                    scores=scores.view(Q, k, L), path_score=path.view(Q, k), hit_spans=hits.view(Q, k, 2),
                    hit_seconds=seconds(hits).view(Q, k, 2))

@@ -325,7 +325,8 @@ class EnhancedAudioTextModel(nn.Module):
 
     @torch.no_grad()
     def align(self, input_values, attention_mask_audio, input_ids, attention_mask=None, *, word_ids=None,
-              audio_encoded=None, text_encoded=None, return_matrix=False):
+              audio_encoded=None, text_encoded=None, return_matrix=False, free_ends=False, lead=1, trail=1,
+              spot_bias=0.0):
         """Where in clip b is each token of transcript b, and how confident is the alignment head
         about it (WordLevelAlignmentModule, ref:214-310; needs use_word_alignment, else ValueError).
         One clip is paired with one transcript.  The head-averaged text->audio attention matrix
@@ -343,7 +344,19 @@ class EnhancedAudioTextModel(nn.Module):
         path's summed log alignment weight; matrix fp32 [B, L, T] with return_matrix=True; and with
         word_ids (int [B, L], a fast tokenizer's word_ids(), -1 for special and padding tokens)
         word_spans / word_seconds [B, W, 2] and word_scores [B, W], W = max word id + 1: min start to
-        max end and the mean confidence over a word's tokens, (-1, -1) for an unused word id."""
+        max end and the mean confidence over a word's tokens, (-1, -1) for an unused word id.
+
+        free_ends=True is for a transcript that is a fragment of what the clip says: the
+        same matrix is decoded with both ends free.  The phrase is tokens lead .. n-1-trail (without
+        its <s> / </s> by default); a frame inside the hit gains log weight - bg with bg = -log(valid
+        frames) + spot_bias, i.e. at spot_bias = 0 it gains exactly when its token attends to it more
+        than uniformly (spot_bias is the caller's log-odds threshold), and the frames around the hit
+        cost nothing.  token_spans then cover the phrase tokens only ((-1, -1) on the lead / trail
+        tokens too, so word_* skip them), the dict also has hit_spans int32 [B, 2] / hit_seconds, the
+        phrase's first frame and last frame + 1, and path_score is the summed gain over the hit, a
+        log-likelihood ratio against the background: <= 0 says the phrase beats it nowhere in the
+        clip.  A transcript without a phrase token gives (-1, -1) and -inf.  scores and matrix do not
+        change."""
         if not self.use_word_alignment:
             raise ValueError("align() needs a model built with use_word_alignment=True")
         if attention_mask is None:
@@ -355,11 +368,13 @@ class EnhancedAudioTextModel(nn.Module):
         finally:
             self.training = was_training
         self.store.sync_shadow()
-        return self.engine.align_pairs(th, attention_mask, ah, attention_mask_audio, word_ids, return_matrix)
+        return self.engine.align_pairs(th, attention_mask, ah, attention_mask_audio, word_ids, return_matrix,
+                                       free_ends=free_ends, lead=lead, trail=trail, spot_bias=spot_bias)
 
     @torch.no_grad()
     def locate_clips(self, input_ids, attention_mask, store, candidates, *, word_ids=None, text_encoded=None,
-                     lead=1, trail=1, pair_batch=128, return_matrix=False, return_emit=False):
+                     lead=1, trail=1, pair_batch=128, return_matrix=False, return_emit=False, free_ends=False,
+                     spot_bias=0.0):
         """align() for search hits: where in each of k candidate corpus clips is text
         query i spoken.  store: a retrieval.AudioStateStore(align_rows=True) built from this model with
         its present weights; candidates int [Q, k] are clip ids of the store (-1 = empty), as returned
@@ -375,7 +390,13 @@ class EnhancedAudioTextModel(nn.Module):
         [Q, k, 2] / hit_seconds: the first frame of token `lead` to the end of token n - 1 - trail,
         i.e. the phrase without its <s> / </s>, (-1, -1) when the transcript has fewer than
         lead + trail + 1 tokens.  An empty slot, and a clip with fewer frames than the query has
-        tokens, give (-1, -1) spans and path_score -inf."""
+        tokens, give (-1, -1) spans and path_score -inf.
+
+        free_ends=True, spot_bias: align()'s free-endpoint decode per pair, for a typed
+        phrase that is a fragment of what a clip says: hit_spans / hit_seconds are then the span where
+        the phrase tokens lead .. n-1-trail beat the background -log(clip frames) + spot_bias,
+        token_spans cover those tokens only, and path_score is the summed gain over the hit (<= 0: the
+        clip does not contain the phrase by this measure).  scores, matrix and emit do not change."""
         if not self.use_word_alignment:
             raise ValueError("locate_clips() needs a model built with use_word_alignment=True")
         if attention_mask is None:
@@ -387,7 +408,7 @@ class EnhancedAudioTextModel(nn.Module):
             self.training = was_training
         self.store.sync_shadow()
         return self.engine.locate_clips(th, attention_mask, store, candidates, word_ids, lead, trail, pair_batch,
-                                        return_matrix, return_emit)
+                                        return_matrix, return_emit, free_ends=free_ends, spot_bias=spot_bias)
 
     def _encode_nograd(self, kind, x, mask):
         self.store.sync_shadow()

@@ -853,6 +853,36 @@ def align_decode(emit, ntok, nfrm):
     return spans, score
 
 
+def align_spot(emit, ntok, nfrm, bg, lead=0):
+    """Free-endpoint decode of frame-major emissions (ste_align_spot): where inside pair b's
+    nfrm[b] frames do the ntok[b] phrase tokens of columns lead .. lead + ntok[b] - 1 beat a background
+    of bg[b] per frame.  emit fp32 [B, T, L] (a column view of a wider [B, T, lde] buffer is fine), ntok /
+    nfrm int32 [B], bg fp32 [B] (finite) -> (spans int32 [B, L, 2] as (first frame, last frame + 1), -1
+    outside the phrase's columns; hit int32 [B, 2], the phrase's first frame and last frame + 1; score
+    fp32 [B], the summed gain emit - bg over the hit).  An infeasible pair (no token, more tokens than
+    columns from lead or than frames) is all -1 with score -inf."""
+    if emit.dim() != 3:
+        raise ValueError(f"emit must be [B, T, L], got {tuple(emit.shape)}")
+    B, T, L = emit.shape
+    if not 0 <= int(lead) < max(L, 1):
+        raise ValueError(f"lead must lie in [0, {L}), got {lead}")
+    if emit.dtype != F32 or bg.dtype != F32:
+        raise ValueError(f"emit and bg must be float32, got {emit.dtype} and {bg.dtype}")
+    if ntok.dtype != torch.int32 or nfrm.dtype != torch.int32:
+        raise ValueError(f"ntok and nfrm must be int32, got {ntok.dtype} and {nfrm.dtype}")
+    if ntok.numel() != B or nfrm.numel() != B or bg.numel() != B:
+        raise ValueError(f"ntok, nfrm and bg must have one entry per pair ({B}), got {ntok.numel()}, "
+                         f"{nfrm.numel()}, {bg.numel()}")
+    assert emit.stride(2) == 1 and emit.stride(0) == T * emit.stride(1)
+    assert ntok.is_contiguous() and nfrm.is_contiguous() and bg.is_contiguous()
+    spans = torch.empty(B, L, 2, device=emit.device, dtype=torch.int32)
+    hit = torch.empty(B, 2, device=emit.device, dtype=torch.int32)
+    score = torch.empty(B, device=emit.device, dtype=F32)
+    call("ste_align_spot", ptr(emit), emit.stride(1), ptr(ntok), ptr(nfrm), ptr(bg), int(lead), B, L, T, ptr(spans),
+         ptr(hit), ptr(score), _s())
+    return spans, hit, score
+
+
 def rank1_bwd(a, w, z, act, out, dw=None, db=None):
     M, K = z.shape
     call("ste_rank1_bwd", ptr(a), ptr(w), ptr(z), M, K, int(act), ptr(out), ptr(dw), ptr(db), _s())

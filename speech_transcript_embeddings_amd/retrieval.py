@@ -514,13 +514,15 @@ def rerank_clips(model, input_ids, attention_mask, store, idx, *, text_encoded=N
 
 
 @torch.no_grad()
-def search_clips(model, store, input_ids, attention_mask, k, *, rerank=True, locate=True, word_ids=None):
+def search_clips(model, store, input_ids, attention_mask, k, *, rerank=True, locate=True, word_ids=None,
+                 free_ends=False, spot_bias=0.0):
     """A typed phrase against an indexed archive, end to end: ONE text-encoder pass per
     query, shared by store.search (stage 1), rerank_clips (stage 2, with rerank=True and a
     use_cross_modal model) and model.locate_clips (where in each hit the phrase is spoken, with
     locate=True; needs a store built with align_rows=True).  Returns (values fp32 [Q, k], indices
     [Q, k], location): the hits in their final (reranked) order and model.locate_clips' dict for
-    exactly those indices, None with locate=False."""
+    exactly those indices, None with locate=False.  free_ends / spot_bias go to model.locate_clips:
+    with free_ends=True the phrase is located as a fragment of what each hit says."""
     if attention_mask is None:
         attention_mask = torch.ones_like(input_ids)
     was_training, model.training = model.training, False   # encode_text reads the flag: no dropout here
@@ -531,8 +533,8 @@ def search_clips(model, store, input_ids, attention_mask, k, *, rerank=True, loc
     vals, idx = store.search(_unit_rows(enc[0]), k)
     if rerank and getattr(model, "use_cross_modal", False):
         vals, idx = rerank_clips(model, input_ids, attention_mask, store, idx, text_encoded=enc)
-    where = model.locate_clips(input_ids, attention_mask, store, idx, word_ids=word_ids, text_encoded=enc) \
-        if locate else None
+    where = model.locate_clips(input_ids, attention_mask, store, idx, word_ids=word_ids, text_encoded=enc,
+                               free_ends=free_ends, spot_bias=spot_bias) if locate else None
     return vals, idx, where
 
 

@@ -36,6 +36,8 @@ through them); the fused training step itself calls the C ABI directly (engine.p
         ste::align_matrix_seg on rows stored as MX-fp8 bytes and E8M0 block scales (DESIGN §21)
     ste::align_decode(emit, ntok, nfrm) -> (spans, score)
         monotone (Viterbi) decode of that log matrix into one frame span per token
+    ste::align_spot(emit, ntok, nfrm, bg, lead=0) -> (spans, hit, score)
+        the same decode with both ends free against a per-pair background: phrase spotting
 
 Every op fails loudly (SteError) without the HIP library; there is no CPU implementation.
 """
@@ -468,5 +470,22 @@ def _align_decode_fake(emit, ntok, nfrm):
     return emit.new_empty(B, L, 2, dtype=torch.int32), emit.new_empty(B, dtype=F32)
 
 
+@torch.library.custom_op("ste::align_spot", mutates_args=())
+def align_spot(emit: Tensor, ntok: Tensor, nfrm: Tensor, bg: Tensor, lead: int = 0) -> tuple[Tensor, Tensor, Tensor]:
+    """Free-endpoint decode of emit fp32 [B, T, L]: where in nfrm[b] frames do the ntok[b] phrase tokens
+    of columns lead.. beat a background of bg[b] per frame -> (spans int32 [B, L, 2], -1
+    outside the phrase; hit int32 [B, 2]; score fp32 [B], the summed gain over the hit).  Forward only."""
+    return ops.align_spot(emit.float().contiguous(), ntok.to(torch.int32).contiguous(),
+                          nfrm.to(torch.int32).contiguous(), bg.float().contiguous(), int(lead))
+
+
+@align_spot.register_fake
+def _align_spot_fake(emit, ntok, nfrm, bg, lead=0):
+    B, _, L = emit.shape
+    return (emit.new_empty(B, L, 2, dtype=torch.int32), emit.new_empty(B, 2, dtype=torch.int32),
+            emit.new_empty(B, dtype=F32))
+
+
 OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim", "xattn_mq",
-       "xattn_seg", "xattn_seg_mx8", "align_matrix", "align_matrix_seg", "align_matrix_seg_mx8", "align_decode")
+       "xattn_seg", "xattn_seg_mx8", "align_matrix", "align_matrix_seg", "align_matrix_seg_mx8", "align_decode",
+       "align_spot")
