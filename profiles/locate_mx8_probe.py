@@ -7,7 +7,7 @@ Q = 64 text queries, k = 10 candidate clips each, P = 768, 4 alignment heads, L 
 T = 500 (10 s) and 1500 (30 s) frames.  Two draws of the candidate lists: "distinct" (640 different
 clips) and "skewed" (one hub clip in every list, the other 576 candidates different clips).
 
-(a) kernel: one ops.align_matrix_seg_mx8_fwd launch (matrix, emit and out) over the e4m3 bytes and E8M0
+(a) kernel: one ops.align_matrix_seg_fwd(scales=...) launch (matrix, emit and out) over the e4m3 bytes and E8M0
     scales of 640 clips against one ops.align_matrix_seg_fwd launch over the bf16 rows of the same clips
     (the dequantised bytes, so the two launches compute the same bits: bits_equal).
 (b) end to end at T = 500, full-size model with random weights: model.locate_clips on a store built with
@@ -88,8 +88,8 @@ def kernel_step(T, iters, rounds):
         pseg = idx.reshape(-1).contiguous()
 
         def mx8():
-            ops.align_matrix_seg_mx8_fwd(q, qblk, pseg, kv8, sc8, seg_row, seg_len, L, T, NH, matrix=new[0],
-                                         emit=new[1], out=new[2])
+            ops.align_matrix_seg_fwd(q, qblk, pseg, kv8, seg_row, seg_len, L, T, NH, scales=sc8, matrix=new[0],
+                                     emit=new[1], out=new[2])
 
         def bf():
             ops.align_matrix_seg_fwd(q, qblk, pseg, kv, seg_row, seg_len, L, T, NH, matrix=old[0], emit=old[1],

@@ -6,7 +6,7 @@ The shapes and draws of clip_rerank_probe.py: Q = 64 text queries, k = 10 candid
 P = 768, 8 heads, L = 64 tokens, clips of T = 500 (10 s) and 1500 (30 s) frames; "distinct" (640
 different clips) and "skewed" (one hub clip in every list).
 
-(a) kernel: one ops.xattn_seg_mx8_fwd launch over the e4m3 bytes and E8M0 scales against one
+(a) kernel: one ops.xattn_seg_fwd(ks=, vs=) launch over the e4m3 bytes and E8M0 scales against one
     ops.xattn_seg_fwd launch over the bf16 rows those bytes were quantised from, in ms and in TB/s of
     the bytes each one reads (the K and V head slices of the distinct segments: G·T·4P for bf16,
     G·T·(2P + P/16) for mx8).
@@ -63,8 +63,8 @@ def kernel_step(T, iters, rounds):
                               plan["tile_cnt"], NH, out_bf)
 
         def mx():
-            ops.xattn_seg_mx8_fwd(q, plan["qrow"], plan["pseg"], kq[:, :P], kq[:, P:], ksc[:, :P // 32],
-                                  ksc[:, P // 32:], srow, slen, plan["tile_first"], plan["tile_cnt"], NH, out_mx)
+            ops.xattn_seg_fwd(q, plan["qrow"], plan["pseg"], kq[:, :P], kq[:, P:], srow, slen, plan["tile_first"],
+                              plan["tile_cnt"], NH, out_mx, ks=ksc[:, :P // 32], vs=ksc[:, P // 32:])
 
         bf()
         mx()

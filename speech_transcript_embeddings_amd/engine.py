@@ -1157,6 +1157,45 @@ class Engine:
         _lib.call("ste_mask_i64_to_f32", mask_i64.contiguous().data_ptr(), None, m.data_ptr(), n, _lib.stream_ptr())
         return m
 
+    def _frame_mask32(self, amask, B, T):
+        """An audio mask as int32 [B*T] frames (None stays None): a sample-level wav2vec2 mask [B, N]
+        goes through the conv stack's frame_mask, a frame mask [B, T] of any integer dtype through _mask32."""
+        if amask is None:
+            return None
+        if self.raw_audio and amask.shape[-1] != T:
+            from .wav2vec2 import frame_mask
+            return frame_mask(self.acfg, amask, B, amask.shape[-1], T, self.s.device)[1]
+        return self._mask32(amask.to(self.s.device, torch.int64), B * T)
+
+    def _unit(self, x):
+        y = self._e(*x.shape)
+        ops.l2norm_fwd(x, y, self._e(x.shape[0]))
+        return y
+
+    def _frames_to_seconds(self, spans):
+        return torch.where(spans < 0, -1.0, spans.float() * self.frame_seconds)
+
+    def _fused_pair_scores(self, att, scores, *, tproj, trows, aproj, arows, qa, arow, kvt, kvblk, tm32, L, live):
+        """The tail of score_pairs and score_clips, from the text -> audio attention output att [R, P] to
+        the pair scores: out_proj and the text side's [projection | attended] rows, the audio -> text
+        attention (row arow[r] of qa over text block kvblk[r], int32, negative = empty pair) and the audio
+        side's, the two fusions, and the cosine of pair live[r]'s fused rows into scores [R].  trows /
+        arows int64 [R]: the row of tproj / aproj of each pair."""
+        s, P = self.s, self.m.projection_dim
+        R = att.shape[0]
+        tcat, acat = self._e(R, 2 * P), self._e(R, 2 * P)
+        ops.linear(att, self._w32("text_to_audio_attention.out_proj.weight"),
+                   s.p("text_to_audio_attention.out_proj.bias"), out=tcat[:, P:])
+        ops.copy2d(tcat[:, :P], tproj.index_select(0, trows))
+        ops.xattn_gather_fwd(qa, arow, kvt[:, :P], kvt[:, P:], kvblk, tm32, R, L, self.m.xattn_heads, att)
+        ops.linear(att, self._w32("audio_to_text_attention.out_proj.weight"),
+                   s.p("audio_to_text_attention.out_proj.bias"), out=acat[:, P:])
+        ops.copy2d(acat[:, :P], aproj.index_select(0, arows))
+        tfused, _ = self._fuse_fwd("text_fusion", tcat)
+        afused, _ = self._fuse_fwd("audio_fusion", acat)
+        ops.topk_target_score(self._unit(afused), self._unit(tfused), live, scores)
+        return scores
+
     def cross_forward(self, tproj, th, tmask, aproj, ah, amask, train, seed):
         """apply_cross_modal_attention (ref:643-682) for one call: text [b,P] + hidden [b,L,Ht],
         audio [b,P] + hidden [b,T,Ha] -> (text_fused, audio_fused) [b,P] fp32 and the saved
@@ -1170,12 +1209,7 @@ class Engine:
         thb = ops.cast_bf16(th.contiguous(), self._e(b * L, Ht, dtype=BF16))
         ahb = ops.cast_bf16(ah.contiguous(), self._e(b * T, Ha, dtype=BF16))
         tm32 = self._mask32(tmask, b * L) if tmask is not None else None
-        if amask is not None and self.raw_audio and amask.shape[-1] != T:
-            # a sample-level wav2vec2 mask [b, N]: the frame mask of the conv stack
-            from .wav2vec2 import frame_mask
-            am32 = frame_mask(self.acfg, amask, b, amask.shape[-1], T, self.s.device)[1]
-        else:
-            am32 = self._mask32(amask, b * T) if amask is not None else None
+        am32 = self._frame_mask32(amask, b, T)
         kva, aseqb = self._kv("text_to_audio_attention", "audio_seq_to_projection", ahb)
         tcat, tx = self._xq_fwd("text_to_audio_attention", tproj.float().contiguous(), kva, am32, b, T,
                                 (_site_seed(seed, 1),), p_x)
@@ -1206,38 +1240,22 @@ class Engine:
         U, L, Ht = th.shape
         B, T, Ha = ah.shape
         P = m.projection_dim
-        cand = candidates.to(dev, torch.int32).contiguous()
-        if cand.dim() != 2 or cand.shape[0] != B or cand.shape[1] < 1:
-            raise ValueError(f"candidates must be [{B}, C >= 1], got {tuple(cand.shape)}")
+        cand, _, _ = _candidates(candidates, B, U, "C", dev)
         C = cand.shape[1]
-        lo, hi = (int(x) for x in torch.stack((cand.min(), cand.max())).tolist())
-        if lo < -1 or hi >= U:
-            raise ValueError(f"candidates must lie in [-1, {U}), got [{lo}, {hi}]")
         if audio_context is not None and not 0 <= int(audio_context) < C:
             raise ValueError(f"audio_context must be a column of candidates, got {audio_context}")
         R = B * C
         slot = cand.view(-1)
         tproj, aproj = tproj.float().contiguous(), aproj.float().contiguous()
         scores = torch.full((R,), float("-inf"), device=dev, dtype=F32)
-
-        def unit(x):
-            y = self._e(*x.shape)
-            ops.l2norm_fwd(x, y, self._e(x.shape[0]))
-            return y
-
         arep = torch.arange(B, device=dev, dtype=torch.int32).repeat_interleave(C)   # clip of each pair
         if not m.use_cross_modal:
-            ops.topk_target_score(unit(aproj).index_select(0, arep.long()), unit(tproj), slot, scores)
+            ops.topk_target_score(self._unit(aproj).index_select(0, arep.long()), self._unit(tproj), slot, scores)
             return scores.view(B, C)
-        nh = m.xattn_heads
         thb = ops.cast_bf16(th.contiguous(), self._e(U * L, Ht, dtype=BF16))
         ahb = ops.cast_bf16(ah.contiguous(), self._e(B * T, Ha, dtype=BF16))
         tm32 = self._mask32(tmask, U * L) if tmask is not None else None
-        if amask is not None and self.raw_audio and amask.shape[-1] != T:
-            from .wav2vec2 import frame_mask   # a sample-level wav2vec2 mask, as in cross_forward
-            am32 = frame_mask(self.acfg, amask, B, amask.shape[-1], T, dev)[1]
-        else:
-            am32 = self._mask32(amask, B * T) if amask is not None else None
+        am32 = self._frame_mask32(amask, B, T)
         kva, _ = self._kv("text_to_audio_attention", "audio_seq_to_projection", ahb)    # once per clip
         kvt, _ = self._kv("audio_to_text_attention", "text_seq_to_projection", thb)     # once per transcript
         s = self.s
@@ -1249,20 +1267,11 @@ class Engine:
         ctx_t = slot if audio_context is None else cand[:, int(audio_context)].repeat_interleave(C)
         kvblk = torch.where(slot < 0, slot, ctx_t).contiguous()
         live = torch.where(kvblk < 0, kvblk, torch.arange(R, device=dev, dtype=torch.int32))
-        tcat, acat = self._e(R, 2 * P), self._e(R, 2 * P)
         att = self._e(R, P)
-        ops.xattn_mq_fwd(qt, slot, kva[:, :P], kva[:, P:], am32, B, C, T, nh, att)
-        ops.linear(att, self._w32("text_to_audio_attention.out_proj.weight"),
-                   s.p("text_to_audio_attention.out_proj.bias"), out=tcat[:, P:])
-        ops.copy2d(tcat[:, :P], tproj.index_select(0, slot.clamp(min=0).long()))
-        ops.xattn_gather_fwd(qa, arep, kvt[:, :P], kvt[:, P:], kvblk, tm32, R, L, nh, att)
-        ops.linear(att, self._w32("audio_to_text_attention.out_proj.weight"),
-                   s.p("audio_to_text_attention.out_proj.bias"), out=acat[:, P:])
-        ops.copy2d(acat[:, :P], aproj.index_select(0, arep.long()))
-        tfused, _ = self._fuse_fwd("text_fusion", tcat)
-        afused, _ = self._fuse_fwd("audio_fusion", acat)
-        ops.topk_target_score(unit(afused), unit(tfused), live, scores)
-        return scores.view(B, C)
+        ops.xattn_mq_fwd(qt, slot, kva[:, :P], kva[:, P:], am32, B, C, T, m.xattn_heads, att)
+        return self._fused_pair_scores(att, scores, tproj=tproj, trows=slot.clamp(min=0).long(), aproj=aproj,
+                                       arows=arep.long(), qa=qa, arow=arep, kvt=kvt, kvblk=kvblk, tm32=tm32, L=L,
+                                       live=live).view(B, C)
 
     @torch.no_grad()
     def score_clips(self, tproj, th, tmask, store, candidates):
@@ -1280,31 +1289,19 @@ class Engine:
         m, dev, s = self.m, self.s.device, self.s
         Q, L, Ht = th.shape
         P = m.projection_dim
-        cand = candidates.to(dev, torch.int32).contiguous()
-        if cand.dim() != 2 or cand.shape[0] != Q or cand.shape[1] < 1:
-            raise ValueError(f"candidates must be [{Q}, k >= 1], got {tuple(cand.shape)}")
-        lo, hi = (int(x) for x in torch.stack((cand.min(), cand.max())).tolist())
-        if lo < -1 or hi >= len(store):
-            raise ValueError(f"candidates must lie in [-1, {len(store)}), got [{lo}, {hi}]")
+        cand, _, hi = _candidates(candidates, Q, len(store), "k", dev)
         store.check()
         k = cand.shape[1]
         R = Q * k
         tproj = tproj.float().contiguous()
-
-        def unit(x):
-            y = self._e(*x.shape)
-            ops.l2norm_fwd(x, y, self._e(x.shape[0]))
-            return y
-
         if not m.use_cross_modal:
             scores = torch.full((R,), float("-inf"), device=dev, dtype=F32)
-            qs = unit(tproj).repeat_interleave(k, 0)
+            qs = self._unit(tproj).repeat_interleave(k, 0)
             for base, rows in store.index.chunks:
                 ops.topk_target_score(qs, rows, cand.view(-1), scores, index_base=base)
             return scores.view(Q, k)
         if hi < 0:
             return torch.full((Q, k), float("-inf"), device=dev, dtype=F32)
-        nh = m.xattn_heads
         plan = plan_clip_pairs(cand)
         qrow, pseg = plan["qrow"], plan["pseg"]
         clips = plan["unique"].long()
@@ -1317,26 +1314,15 @@ class Engine:
         qa = ops.linear(aproj, self._w32("audio_to_text_attention.query.weight"),
                         s.p("audio_to_text_attention.query.bias"))
         live = torch.where(pseg < 0, pseg, torch.arange(R, device=dev, dtype=torch.int32))
-        tcat, acat = self._e(R, 2 * P), self._e(R, 2 * P)
         att = self._e(R, P)
-        seg = (store.seg_row.index_select(0, clips), store.frames.index_select(0, clips), plan["tile_first"],
-               plan["tile_cnt"], nh, att)
-        if store.kv_dtype == "mx8":   # the same pairs over the stored e4m3 bytes and their block scales
-            ops.xattn_seg_mx8_fwd(qt, qrow, pseg, store.kv[:, :P], store.kv[:, P:], store.kv_scales[:, :P // 32],
-                                  store.kv_scales[:, P // 32:], *seg)
-        else:
-            ops.xattn_seg_fwd(qt, qrow, pseg, store.kv[:, :P], store.kv[:, P:], *seg)
-        ops.linear(att, self._w32("text_to_audio_attention.out_proj.weight"),
-                   s.p("text_to_audio_attention.out_proj.bias"), out=tcat[:, P:])
-        ops.copy2d(tcat[:, :P], tproj.index_select(0, qrow.clamp(min=0).long()))
-        ops.xattn_gather_fwd(qa, pseg, kvt[:, :P], kvt[:, P:], qrow, tm32, R, L, nh, att)
-        ops.linear(att, self._w32("audio_to_text_attention.out_proj.weight"),
-                   s.p("audio_to_text_attention.out_proj.bias"), out=acat[:, P:])
-        ops.copy2d(acat[:, :P], aproj.index_select(0, pseg.clamp(min=0).long()))
-        tfused, _ = self._fuse_fwd("text_fusion", tcat)
-        afused, _ = self._fuse_fwd("audio_fusion", acat)
+        kx, vx, scales = store.kv_bank.xattn_operands()   # bf16 rows, or e4m3 bytes and their scales (§19)
+        ops.xattn_seg_fwd(qt, qrow, pseg, kx, vx, store.seg_row.index_select(0, clips),
+                          store.frames.index_select(0, clips), plan["tile_first"], plan["tile_cnt"], m.xattn_heads, att,
+                          **scales)
         scores = torch.full((R,), float("-inf"), device=dev, dtype=F32)
-        ops.topk_target_score(unit(afused), unit(tfused), live, scores)
+        self._fused_pair_scores(att, scores, tproj=tproj, trows=qrow.clamp(min=0).long(), aproj=aproj,
+                                arows=pseg.clamp(min=0).long(), qa=qa, arow=pseg, kvt=kvt, kvblk=qrow, tm32=tm32, L=L,
+                                live=live)
         return scores.index_select(0, plan["inverse"].view(-1)).view(Q, k)
 
     def cross_backward(self, sv, d_tf, d_af):
@@ -1393,6 +1379,24 @@ class Engine:
         bg = -torch.log(nfrm.clamp(min=1).to(F32)) + float(spot_bias)
         return ops.align_spot(emit, m.contiguous(), nfrm, bg.contiguous(), lead)
 
+    def _align_result(self, spans, scores, path, hits=None, matrix=None, word_ids=None, shape=None):
+        """The dict align_pairs and locate_clips return, from per-pair rows: token spans / seconds, scores,
+        path score, hit spans / seconds and the matrix where given, and the word-level entries with
+        word_ids int [R, L].  shape = (Q, k) views every entry [R, ...] as [Q, k, ...]."""
+        from .align import words_from_tokens
+        sec = self._frames_to_seconds
+        out = dict(token_spans=spans, token_seconds=sec(spans), scores=scores, path_score=path)
+        if hits is not None:
+            out.update(hit_spans=hits, hit_seconds=sec(hits))
+        if matrix is not None:
+            out["matrix"] = matrix
+        if word_ids is not None:
+            ws, wsc = words_from_tokens(spans, scores, word_ids)
+            out.update(word_spans=ws, word_seconds=sec(ws), word_scores=wsc)
+        if shape is not None:
+            out = {name: t.view(*shape, *t.shape[1:]) for name, t in out.items()}
+        return out
+
     @torch.no_grad()
     def align_pairs(self, th, tmask, ah, amask, word_ids=None, return_matrix=False, *, free_ends=False, lead=1,
                     trail=1, spot_bias=0.0):
@@ -1404,7 +1408,7 @@ class Engine:
         (checked on the device, one sync).  Inference arithmetic, nothing saved.  free_ends=True
         decodes the same emissions with ops.align_spot instead (_spot; lead, trail and
         spot_bias are read in this mode only).  -> dict, see EnhancedAudioTextModel.align."""
-        from .align import align_infer, words_from_tokens
+        from .align import align_infer
         dev = self.s.device
         B, L, Ht = th.shape
         T, Ha = ah.shape[1], ah.shape[2]
@@ -1412,11 +1416,7 @@ class Engine:
             raise ValueError(f"align pairs clip b with transcript b: {ah.shape[0]} clips, {B} transcripts")
         tm = (torch.ones(B, L, dtype=torch.int64, device=dev) if tmask is None
               else tmask.to(dev, torch.int64).contiguous())
-        if amask is not None and self.raw_audio and amask.shape[-1] != T:
-            from .wav2vec2 import frame_mask   # a sample-level wav2vec2 mask, as in cross_forward
-            am32 = frame_mask(self.acfg, amask, B, amask.shape[-1], T, dev)[1]
-        else:
-            am32 = self._mask32(amask, B * T) if amask is not None else None
+        am32 = self._frame_mask32(amask, B, T)
         bad = (tm[:, 1:] > tm[:, :-1]).any()
         if am32 is not None:
             fm = am32.view(B, T)
@@ -1431,24 +1431,12 @@ class Engine:
         ahb = ops.cast_bf16(ah.reshape(B * T, Ha).float().contiguous(), self._e(B * T, Ha, dtype=BF16))
         scores, matrix, emit = align_infer(self, thf, thb, ahb, B, L, T, {"a_mask32": am32, "_tmask_i64": tm},
                                            want_matrix=return_matrix, want_emit=True)
-        fs = self.frame_seconds
-
-        def seconds(sp):
-            return torch.where(sp < 0, -1.0, sp.float() * fs)
-
         if free_ends:
             spans, hits, path = self._spot(emit, ntok, nfrm, lead, trail, spot_bias)
         else:
-            spans, path = ops.align_decode(emit, ntok, nfrm)
-        out = dict(token_spans=spans, token_seconds=seconds(spans), scores=scores, path_score=path)
-        if free_ends:
-            out.update(hit_spans=hits, hit_seconds=seconds(hits))
-        if return_matrix:
-            out["matrix"] = matrix
-        if word_ids is not None:
-            ws, wsc = words_from_tokens(spans, scores, word_ids.to(dev))
-            out.update(word_spans=ws, word_seconds=seconds(ws), word_scores=wsc)
-        return out
+            (spans, path), hits = ops.align_decode(emit, ntok, nfrm), None
+        return self._align_result(spans, scores, path, hits, matrix if return_matrix else None,
+                                  None if word_ids is None else word_ids.to(dev))
 
     @torch.no_grad()
     def locate_clips(self, th, tmask, store, candidates, word_ids=None, lead=1, trail=1, pair_batch=128,
@@ -1460,12 +1448,11 @@ class Engine:
         RuntimeError); candidates int [Q,k] of clip ids in [-1, len(store)), -1 = empty slot.
 
         The head's queries are projected once per query; pair (i, n) runs query block i over clip n's
-        stored alignment K|V rows in place (ops.align_matrix_seg_fwd, or ops.align_matrix_seg_mx8_fwd on
-        a store built with align_dtype="mx8"; the clip ids being the segment indices of the store's
-        own table), then align.confidence_tail and ops.align_decode with ntok
-        from the query and nfrm from the clip.  The pairs run in chunks of pair_batch, which bounds
-        the emissions buffer at pair_batch·Tmax·L·4 bytes; Tmax, the longest candidate clip, comes
-        with the one device -> host sync of the argument checks.
+        stored alignment K|V rows in place (ops.align_matrix_seg_fwd on the alignment bank's operands,
+        whichever its dtype; the clip ids being the segment indices of the store's own table), then
+        align.confidence_tail and ops.align_decode with ntok from the query and nfrm from the clip.  The
+        pairs run in chunks of pair_batch, which bounds the emissions buffer at pair_batch·Tmax·L·4 bytes;
+        Tmax, the longest candidate clip, comes with the one device -> host sync of the argument checks.
 
         -> dict of [Q, k, ...] tensors: token_spans int32 [Q,k,L,2] and token_seconds, scores fp32
         [Q,k,L], path_score fp32 [Q,k], hit_spans int32 [Q,k,2] and hit_seconds (align.hit_spans:
@@ -1480,7 +1467,7 @@ class Engine:
         (-1, -1) on the lead / trail tokens and the padding, hit_spans the kernel's hit, and path_score the
         summed gain over the hit (a log-likelihood ratio; <= 0: the phrase nowhere beats the
         background); scores, matrix and emit are the default mode's bits."""
-        from .align import confidence_tail, hit_spans, text_queries, words_from_tokens
+        from .align import confidence_tail, hit_spans, text_queries
         m, dev = self.m, self.s.device
         if not m.use_word_alignment:
             raise ValueError("locate_clips needs a model built with use_word_alignment=True")
@@ -1488,31 +1475,22 @@ class Engine:
             raise ValueError("locate_clips needs an AudioStateStore built with align_rows=True")
         Q, L, Ht = th.shape
         P = m.projection_dim
-        cand = candidates.to(dev, torch.int32).contiguous()
-        if cand.dim() != 2 or cand.shape[0] != Q or cand.shape[1] < 1:
-            raise ValueError(f"candidates must be [{Q}, k >= 1], got {tuple(cand.shape)}")
-        k = cand.shape[1]
-        R = Q * k
         N = len(store)
         tm = (torch.ones(Q, L, dtype=torch.int64, device=dev) if tmask is None
               else tmask.to(dev, torch.int64).contiguous())
+        cand = _candidate_lists(candidates, Q, "k", dev)
+        k = cand.shape[1]
+        R = Q * k
         pseg = cand.view(-1)
         live = (pseg >= 0) & (pseg < N)          # a clip id outside the store is refused below, never looked up
         nfrm = (store.frames.index_select(0, torch.where(live, pseg, 0).long()) * live if N
                 else torch.zeros(R, dtype=torch.int32, device=dev)).to(torch.int32)
         bad = (tm[:, 1:] > tm[:, :-1]).any()
-        lo, hi, bad, Tmax = (int(x) for x in torch.stack((cand.min(), cand.max(), bad.to(torch.int32),
-                                                           nfrm.max())).tolist())
-        if lo < -1 or hi >= N:
-            raise ValueError(f"candidates must lie in [-1, {N}), got [{lo}, {hi}]")
+        # the text-mask check and the longest candidate clip come with the candidates' one sync
+        _, _, _, bad, Tmax = _candidates(cand, Q, N, "k", dev, (bad.to(torch.int32), nfrm.max()))
         if bad:
             raise ValueError("locate_clips needs prefix text masks (right-padded transcripts)")
         store.check()
-        fs = self.frame_seconds
-
-        def seconds(sp):
-            return torch.where(sp < 0, -1.0, sp.float() * fs)
-
         qblk = torch.where(live, torch.arange(R, device=dev, dtype=torch.int32) // k, -1).to(torch.int32)
         ntok = ((tm != 0).sum(1, dtype=torch.int32).repeat_interleave(k) * live).to(torch.int32)
         spans = torch.full((R, L, 2), -1, dtype=torch.int32, device=dev)
@@ -1527,6 +1505,7 @@ class Engine:
             thf = th.reshape(Q * L, Ht).float().contiguous()
             q = text_queries(self, ops.cast_bf16(thf, self._e(Q * L, Ht, dtype=BF16)))      # once per query
             seg_row, seg_len = store.seg_row, store.frames
+            akv, scales = store.align_bank.align_operands()   # bf16 rows, or e4m3 bytes + scales, in place (§21)
             step = max(int(pair_batch), 1)
             for r0 in range(0, R, step):
                 r1 = min(r0 + step, R)
@@ -1534,13 +1513,8 @@ class Engine:
                 qb, row = qblk[r0:r1].contiguous(), qblk[r0:r1].clamp(min=0).long()
                 emit = emit_all[r0:r1] if return_emit else self._e(n, Tmax, L)
                 att = self._e(n * L, P, dtype=BF16)
-                outs = dict(matrix=None if matrix is None else matrix[r0:r1], emit=emit, out=att)
-                if getattr(store, "align_dtype", "bf16") == "mx8":   # e4m3 bytes + E8M0 scales, read in place (§21)
-                    ops.align_matrix_seg_mx8_fwd(q, qb, pseg[r0:r1].contiguous(), store.akv, store.akv_scales, seg_row,
-                                                 seg_len, L, Tmax, nh, **outs)
-                else:
-                    ops.align_matrix_seg_fwd(q, qb, pseg[r0:r1].contiguous(), store.akv, seg_row, seg_len, L, Tmax,
-                                             nh, **outs)
+                ops.align_matrix_seg_fwd(q, qb, pseg[r0:r1].contiguous(), akv, seg_row, seg_len, L, Tmax, nh,
+                                         matrix=None if matrix is None else matrix[r0:r1], emit=emit, out=att, **scales)
                 th_rows = thf.view(Q, L, Ht).index_select(0, row).view(n * L, Ht)
                 tm_rows = (tm.index_select(0, row) * (qb >= 0).view(n, 1)).contiguous()
                 scores[r0:r1] = confidence_tail(self, att, th_rows, tm_rows, n * L).view(n, L)
@@ -1552,19 +1526,10 @@ class Engine:
                                                                  nfrm[r0:r1].contiguous())
         if not free_ends:
             hits = hit_spans(spans, ntok, lead, trail)
-        out = dict(token_spans=spans.view(Q, k, L, 2), token_seconds=seconds(spans).view(Q, k, L, 2),
-                   scores=scores.view(Q, k, L), path_score=path.view(Q, k), hit_spans=hits.view(Q, k, 2),
-                   hit_seconds=seconds(hits).view(Q, k, 2))
-        if return_matrix:
-            out["matrix"] = matrix.view(Q, k, L, Tm)
+        out = self._align_result(spans, scores, path, hits, matrix,
+                                 None if word_ids is None else word_ids.to(dev).repeat_interleave(k, 0), (Q, k))
         if return_emit:
             out["emit"] = emit_all.view(Q, k, Tm, L)
-        if word_ids is not None:
-            wid = word_ids.to(dev).repeat_interleave(k, 0)
-            ws, wsc = words_from_tokens(spans, scores, wid)
-            W = ws.shape[1]
-            out.update(word_spans=ws.view(Q, k, W, 2), word_seconds=seconds(ws).view(Q, k, W, 2),
-                       word_scores=wsc.view(Q, k, W))
         return out
 
     # ============================================================== full step
@@ -1661,6 +1626,24 @@ class Engine:
             if stage_done:
                 stage_done("text")
         ctx.clear()
+
+
+def _candidate_lists(candidates, rows, name, device=None):
+    """Candidate lists as int32, contiguous, on device, of shape [rows, name >= 1], else ValueError."""
+    cand = candidates.to(device=device, dtype=torch.int32).contiguous()
+    if cand.dim() != 2 or cand.shape[0] != rows or cand.shape[1] < 1:
+        raise ValueError(f"candidates must be [{rows}, {name} >= 1], got {tuple(cand.shape)}")
+    return cand
+
+
+def _candidates(candidates, rows, n, name, device=None, more=()):
+    """_candidate_lists, then the values in [-1, n), else ValueError, in ONE device -> host transfer that
+    also reads the 0-d integer tensors of more.  -> (cand, lo, hi, *their values)."""
+    cand = _candidate_lists(candidates, rows, name, device)
+    lo, hi, *rest = (int(x) for x in torch.stack((cand.min(), cand.max(), *more)).tolist())
+    if lo < -1 or hi >= n:
+        raise ValueError(f"candidates must lie in [-1, {n}), got [{lo}, {hi}]")
+    return (cand, lo, hi, *rest)
 
 
 def _copy_f32(src, dst):

@@ -13,6 +13,7 @@ leaves the parameter gradients in `param.grad` (views of the flat gradient buffe
 """
 from __future__ import annotations
 
+import contextlib
 import logging
 
 import torch
@@ -267,6 +268,16 @@ class EnhancedAudioTextModel(nn.Module):
             return self._encode_nograd("audio", x, mask)
         return _EncodeFn.apply(self, "audio", x, mask, self.store.master[:1].detach().requires_grad_(True))
 
+    @contextlib.contextmanager
+    def _eval_arithmetic(self):
+        """Inference arithmetic for the block: encode_* read the training flag, so it is forced off (no
+        dropout) and restored on the way out."""
+        was_training, self.training = self.training, False
+        try:
+            yield
+        finally:
+            self.training = was_training
+
     def apply_cross_modal_attention(self, text_projected, text_hidden, text_mask, audio_projected, audio_hidden,
                                     audio_mask):
         """ref:643-682: (text_fused [B,P], audio_fused [B,P]); identity without use_cross_modal."""
@@ -292,13 +303,10 @@ class EnhancedAudioTextModel(nn.Module):
         Forward only, inference arithmetic."""
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
-        was_training, self.training = self.training, False   # encode_* read the flag: no dropout here
-        try:
+        with self._eval_arithmetic():
             aproj, ah = audio_encoded or self.encode_audio(input_values, attention_mask_audio)
             parts = [self.encode_text(input_ids[i:i + text_batch], attention_mask[i:i + text_batch])
                      for i in range(0, input_ids.shape[0], text_batch)]
-        finally:
-            self.training = was_training
         tproj, th = (torch.cat([p[j] for p in parts]) for j in (0, 1)) if len(parts) > 1 else parts[0]
         self.store.sync_shadow()
         return self.engine.score_pairs(tproj, th, attention_mask, aproj, ah, attention_mask_audio, candidates,
@@ -315,11 +323,8 @@ class EnhancedAudioTextModel(nn.Module):
         mode, to skip the text pass.  Forward only, inference arithmetic."""
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
-        was_training, self.training = self.training, False   # encode_text reads the flag: no dropout here
-        try:
+        with self._eval_arithmetic():
             tproj, th = text_encoded or self.encode_text(input_ids, attention_mask)
-        finally:
-            self.training = was_training
         self.store.sync_shadow()
         return self.engine.score_clips(tproj, th, attention_mask, store, candidates)
 
@@ -361,12 +366,9 @@ class EnhancedAudioTextModel(nn.Module):
             raise ValueError("align() needs a model built with use_word_alignment=True")
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
-        was_training, self.training = self.training, False   # encode_* read the flag: no dropout here
-        try:
+        with self._eval_arithmetic():
             _, ah = audio_encoded or self.encode_audio(input_values, attention_mask_audio)
             _, th = text_encoded or self.encode_text(input_ids, attention_mask)
-        finally:
-            self.training = was_training
         self.store.sync_shadow()
         return self.engine.align_pairs(th, attention_mask, ah, attention_mask_audio, word_ids, return_matrix,
                                        free_ends=free_ends, lead=lead, trail=trail, spot_bias=spot_bias)
@@ -401,11 +403,8 @@ class EnhancedAudioTextModel(nn.Module):
             raise ValueError("locate_clips() needs a model built with use_word_alignment=True")
         if attention_mask is None:
             attention_mask = torch.ones_like(input_ids)
-        was_training, self.training = self.training, False   # encode_text reads the flag: no dropout here
-        try:
+        with self._eval_arithmetic():
             _, th = text_encoded or self.encode_text(input_ids, attention_mask)
-        finally:
-            self.training = was_training
         self.store.sync_shadow()
         return self.engine.locate_clips(th, attention_mask, store, candidates, word_ids, lead, trail, pair_batch,
                                         return_matrix, return_emit, free_ends=free_ends, spot_bias=spot_bias)

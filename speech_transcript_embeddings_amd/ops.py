@@ -703,11 +703,17 @@ def xattn_gather_fwd(q, qrow, k, v, kvblk, mask, R, S, nh, out):
          float((P // nh) ** -0.5), ptr(out), _s())
 
 
-def xattn_seg_fwd(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, nh, out):
+def xattn_seg_fwd(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, nh, out, *, ks=None, vs=None):
     """Pair r attends with row qrow[r] of q [U, P] over the segment pseg[r]: rows seg_row[g] ..
-    seg_row[g] + seg_len[g] - 1 of k / v (bf16, one buffer).  Pairs sorted by segment, -1 last, cut
-    into tiles of <= 16 pairs of one segment by tile_first / tile_cnt (retrieval.plan_clip_pairs).
-    out fp32 [R, P]; an empty pair or segment gives a zero row.  The arithmetic of xattn_mq_fwd."""
+    seg_row[g] + seg_len[g] - 1 of k / v (one buffer).  Pairs sorted by segment, -1 last, cut into
+    tiles of <= 16 pairs of one segment by tile_first / tile_cnt (retrieval.plan_clip_pairs).
+    out fp32 [R, P]; an empty pair or segment gives a zero row.  The arithmetic of xattn_mq_fwd.
+
+    k / v bf16 [rows, P] and no scales (ste_xattn_seg_fwd), or MX-fp8 rows (ste_xattn_seg_mx8_fwd,
+    DESIGN §19): k / v uint8 views [rows, P] of one buffer of e4m3 bytes with ks / vs uint8 views
+    [rows, P/32] of the buffer of their E8M0 scales (a RowBank's xattn_operands()); the same bits as
+    the bf16 form on the mx8_dequant of those rows.  Here ks / vs must be bytes of one row stride; their
+    width, like P % 32, is left to the library (STE_ERR_SHAPE)."""
     P = q.shape[-1]
     R, G = qrow.numel(), seg_row.numel()
     assert q.dtype == F32 and q.is_contiguous() and out.dtype == F32 and out.shape == (R, P) and out.is_contiguous()
@@ -716,29 +722,16 @@ def xattn_seg_fwd(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, n
     assert tile_first.dtype == torch.int32 and tile_cnt.dtype == torch.int32
     assert tile_first.numel() == tile_cnt.numel()
     assert all(t.is_contiguous() for t in (qrow, pseg, seg_row, seg_len, tile_first, tile_cnt))
-    assert k.dtype == BF16 and v.dtype == BF16 and _ld(k) == _ld(v)
-    call("ste_xattn_seg_fwd", ptr(q), ptr(qrow), ptr(pseg), ptr(k), ptr(v), _ld(k), ptr(seg_row), ptr(seg_len),
-         ptr(tile_first), ptr(tile_cnt), tile_first.numel(), R, G, P, nh, float((P // nh) ** -0.5), ptr(out), _s())
-
-
-def xattn_seg_mx8_fwd(q, qrow, pseg, k, v, ks, vs, seg_row, seg_len, tile_first, tile_cnt, nh, out):
-    """xattn_seg_fwd on MX-fp8 rows: k / v uint8 views [rows, P] of one buffer of e4m3 bytes, ks / vs
-    uint8 views [rows, P/32] of the buffer of their E8M0 scales (an AudioStateStore's kv[:, :P],
-    kv[:, P:], kv_scales[:, :P/32], kv_scales[:, P/32:]).  The same bits as xattn_seg_fwd on the
-    mx8_dequant of those rows."""
-    P = q.shape[-1]
-    R, G = qrow.numel(), seg_row.numel()
-    assert q.dtype == F32 and q.is_contiguous() and out.dtype == F32 and out.shape == (R, P) and out.is_contiguous()
-    assert qrow.dtype == torch.int32 and pseg.dtype == torch.int32 and pseg.numel() == R
-    assert seg_row.dtype == torch.int64 and seg_len.dtype == torch.int32 and seg_len.numel() == G
-    assert tile_first.dtype == torch.int32 and tile_cnt.dtype == torch.int32
-    assert tile_first.numel() == tile_cnt.numel()
-    assert all(t.is_contiguous() for t in (qrow, pseg, seg_row, seg_len, tile_first, tile_cnt))
-    assert k.dtype == torch.uint8 and v.dtype == torch.uint8 and _ld(k) == _ld(v)
-    assert ks.dtype == torch.uint8 and vs.dtype == torch.uint8 and _ld(ks) == _ld(vs)
-    call("ste_xattn_seg_mx8_fwd", ptr(q), ptr(qrow), ptr(pseg), ptr(k), ptr(v), _ld(k), ptr(ks), ptr(vs), _ld(ks),
-         ptr(seg_row), ptr(seg_len), ptr(tile_first), ptr(tile_cnt), tile_first.numel(), R, G, P, nh,
-         float((P // nh) ** -0.5), ptr(out), _s())
+    assert k.dtype == v.dtype and _ld(k) == _ld(v)
+    if k.dtype == BF16:
+        assert ks is None and vs is None
+        name, rows = "ste_xattn_seg_fwd", (ptr(k), ptr(v), _ld(k))
+    else:
+        assert k.dtype == torch.uint8 and ks is not None and vs is not None
+        assert ks.dtype == torch.uint8 and vs.dtype == torch.uint8 and _ld(ks) == _ld(vs)
+        name, rows = "ste_xattn_seg_mx8_fwd", (ptr(k), ptr(v), _ld(k), ptr(ks), ptr(vs), _ld(ks))
+    call(name, ptr(q), ptr(qrow), ptr(pseg), *rows, ptr(seg_row), ptr(seg_len), ptr(tile_first), ptr(tile_cnt),
+         tile_first.numel(), R, G, P, nh, float((P // nh) ** -0.5), ptr(out), _s())
 
 
 def xattn_bwd(q, k, v, probs, dout, B, S, nh, dq, dk, dv, seeds, drop_p=0.0, colsum=None, mask=None):
@@ -791,17 +784,21 @@ def align_matrix_fwd(q, kv, kmask, B, L, T, nh, *, matrix=None, emit=None, out=N
          0 if emit is None else emit.stride(1), ptr(out), 0 if out is None else _ld(out), _s())
 
 
-def align_matrix_seg_fwd(q, qblk, pseg, kv, seg_row, seg_len, L, Tmax, nh, *, matrix=None, emit=None, out=None):
-    """align_matrix_fwd for R (query, segment) pairs over runs of rows of one K|V buffer
-    (ste_align_matrix_seg_fwd): q bf16 [U*L, ldq], qblk / pseg int32 [R] (the pair's query
-    block and segment, negative = empty pair), kv bf16 [rows, 2P] (an AudioStateStore's akv, read in
-    place), seg_row int64 [G] / seg_len int32 [G], Tmax >= every pair's segment length.  Any of matrix
-    fp32 [R, L, Tmax], emit fp32 [R, Tmax, lde >= L] and out bf16 [R*L, ldo]; a pair with F frames
-    writes rows [:F] only, the bits of align_matrix_fwd(B = 1, T = F) on its rows."""
+def align_matrix_seg_fwd(q, qblk, pseg, kv, seg_row, seg_len, L, Tmax, nh, *, scales=None, matrix=None, emit=None,
+                         out=None):
+    """align_matrix_fwd for R (query, segment) pairs over runs of rows of one K|V buffer:
+    q bf16 [U*L, ldq], qblk / pseg int32 [R] (the pair's query block and segment, negative = empty
+    pair), kv [rows, 2P] (a RowBank's align_operands(), read in place), seg_row int64 [G] / seg_len
+    int32 [G], Tmax >= every pair's segment length.  Any of matrix fp32 [R, L, Tmax], emit fp32
+    [R, Tmax, lde >= L] and out bf16 [R*L, ldo]; a pair with F frames writes rows [:F] only, the bits
+    of align_matrix_fwd(B = 1, T = F) on its rows.
+
+    kv bf16 and no scales (ste_align_matrix_seg_fwd), or MX-fp8 rows (ste_align_matrix_seg_mx8_fwd,
+    DESIGN §21): kv uint8 of e4m3 bytes with scales uint8 [rows, 2P/32] of their E8M0 block scales
+    (row-strided views are fine); the same bits as the bf16 form on mx8_dequant(kv, scales)."""
     R, G = qblk.numel(), seg_row.numel()
     P = kv.shape[-1] // 2
-    assert q.dtype == BF16 and kv.dtype == BF16 and q.dim() == 2 and kv.dim() == 2 and q.stride(1) == 1
-    assert kv.stride(1) == 1
+    assert q.dtype == BF16 and q.dim() == 2 and q.stride(1) == 1 and kv.dim() == 2 and kv.stride(1) == 1
     assert qblk.dtype == torch.int32 and pseg.dtype == torch.int32 and pseg.numel() == R
     assert qblk.is_contiguous() and pseg.is_contiguous() and seg_row.is_contiguous() and seg_len.is_contiguous()
     assert seg_row.dtype == torch.int64 and seg_len.dtype == torch.int32 and seg_len.numel() == G
@@ -809,33 +806,17 @@ def align_matrix_seg_fwd(q, qblk, pseg, kv, seg_row, seg_len, L, Tmax, nh, *, ma
     assert emit is None or (emit.dtype == F32 and emit.shape[:2] == (R, Tmax) and emit.stride(2) == 1
                             and emit.stride(0) == Tmax * emit.stride(1))
     assert out is None or (out.dtype == BF16 and out.shape[0] >= R * L and out.stride(1) == 1)
-    call("ste_align_matrix_seg_fwd", ptr(q), _ld(q), ptr(qblk), ptr(pseg), ptr(kv), _ld(kv), ptr(seg_row), ptr(seg_len),
-         R, G, int(L), int(Tmax), P, int(nh), ptr(matrix), ptr(emit), 0 if emit is None else emit.stride(1), ptr(out),
+    if kv.dtype == BF16:
+        assert scales is None
+        name, rows = "ste_align_matrix_seg_fwd", (ptr(kv), _ld(kv))
+    else:
+        assert kv.dtype == torch.uint8 and scales is not None
+        assert scales.dtype == torch.uint8 and scales.dim() == 2 and scales.stride(1) == 1
+        assert scales.shape[0] == kv.shape[0] and scales.shape[1] * 32 == kv.shape[1]
+        name, rows = "ste_align_matrix_seg_mx8_fwd", (ptr(kv), _ld(kv), ptr(scales), _ld(scales))
+    call(name, ptr(q), _ld(q), ptr(qblk), ptr(pseg), *rows, ptr(seg_row), ptr(seg_len), R, G, int(L), int(Tmax), P,
+         int(nh), ptr(matrix), ptr(emit), 0 if emit is None else emit.stride(1), ptr(out),
          0 if out is None else _ld(out), _s())
-
-
-def align_matrix_seg_mx8_fwd(q, qblk, pseg, kv, scales, seg_row, seg_len, L, Tmax, nh, *, matrix=None, emit=None,
-                             out=None):
-    """align_matrix_seg_fwd on MX-fp8 rows (ste_align_matrix_seg_mx8_fwd): kv uint8 [rows, 2P]
-    of e4m3 bytes and scales uint8 [rows, 2P/32] of their E8M0 block scales (an AudioStateStore's akv /
-    akv_scales, read in place; row-strided views are fine).  The other operands and the outputs as
-    align_matrix_seg_fwd; the same bits as that on mx8_dequant(kv, scales)."""
-    R, G = qblk.numel(), seg_row.numel()
-    P = kv.shape[-1] // 2
-    assert q.dtype == BF16 and q.dim() == 2 and q.stride(1) == 1
-    assert kv.dtype == torch.uint8 and kv.dim() == 2 and kv.stride(1) == 1
-    assert scales.dtype == torch.uint8 and scales.dim() == 2 and scales.stride(1) == 1
-    assert scales.shape[0] == kv.shape[0] and scales.shape[1] * 32 == kv.shape[1]
-    assert qblk.dtype == torch.int32 and pseg.dtype == torch.int32 and pseg.numel() == R
-    assert qblk.is_contiguous() and pseg.is_contiguous() and seg_row.is_contiguous() and seg_len.is_contiguous()
-    assert seg_row.dtype == torch.int64 and seg_len.dtype == torch.int32 and seg_len.numel() == G
-    assert matrix is None or (matrix.dtype == F32 and matrix.is_contiguous() and matrix.numel() == R * L * Tmax)
-    assert emit is None or (emit.dtype == F32 and emit.shape[:2] == (R, Tmax) and emit.stride(2) == 1
-                            and emit.stride(0) == Tmax * emit.stride(1))
-    assert out is None or (out.dtype == BF16 and out.shape[0] >= R * L and out.stride(1) == 1)
-    call("ste_align_matrix_seg_mx8_fwd", ptr(q), _ld(q), ptr(qblk), ptr(pseg), ptr(kv), _ld(kv), ptr(scales),
-         _ld(scales), ptr(seg_row), ptr(seg_len), R, G, int(L), int(Tmax), P, int(nh), ptr(matrix), ptr(emit),
-         0 if emit is None else emit.stride(1), ptr(out), 0 if out is None else _ld(out), _s())
 
 
 def align_decode(emit, ntok, nfrm):

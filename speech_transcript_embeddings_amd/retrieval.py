@@ -242,31 +242,95 @@ def plan_clip_pairs(idx: torch.Tensor) -> dict:
 
 
 KV_DTYPES = ("bf16", "mx8")
+ALIGN_MAX_FRAMES = 2048   # the T limit of ste_align_matrix_seg_fwd and ste_align_decode
+
+
+class RowBank:
+    """K|V rows of width 2·dim in one growable buffer, held as bf16 or as MX-fp8:
+      "bf16"  data bf16 [capacity, 2·dim], scales None: 4·dim bytes per row;
+      "mx8"   data uint8 [capacity, 2·dim] of OCP e4m3 bytes + scales uint8 [capacity, 2·dim/32] of E8M0
+              block scales (one per 32 columns), ops.mx8_quant of each bf16 row as it is written:
+              2·dim + dim/16 bytes per row.  Needs dim % 64 == 0.
+    arg is the caller's name for dtype, for the ValueErrors.  held=False is the bank of a store that keeps
+    no such rows: empty, and dim is not checked.  The owner counts the rows in use."""
+
+    def __init__(self, dim: int, dtype: str = "bf16", capacity: int = 0, device="cuda", *, arg: str = "dtype",
+                 held: bool = True):
+        self.bytes_per_frame(dim, dtype, arg)
+        if dtype == "mx8" and held and dim % 64:
+            raise ValueError(f'{arg}="mx8" needs projection_dim % 64 == 0 (MX blocks of 32 over the 2P columns, '
+                             f"quantised 128 at a time), got {dim}")
+        self.dtype, self.device = dtype, torch.device(device)
+        cap = max(int(capacity), 0) if held else 0
+        mx8 = dtype == "mx8"
+        self.data = torch.empty(cap, 2 * dim, device=self.device, dtype=torch.uint8 if mx8 else BF16)
+        self.scales = torch.empty(cap, 2 * dim // 32, device=self.device, dtype=torch.uint8) if mx8 else None
+
+    @staticmethod
+    def bytes_per_frame(dim: int, dtype: str = "bf16", arg: str = "dtype") -> int:
+        """Bytes per stored row of 2·dim columns: "bf16" 4·dim (3,072 at dim = 768); "mx8" 2·dim e4m3
+        bytes + 2·dim/32 E8M0 scale bytes (1,584 at dim = 768, 0.516 of bf16)."""
+        if dtype == "bf16":
+            return 4 * dim
+        if dtype == "mx8":
+            return 2 * dim + 2 * dim // 32
+        raise ValueError(f"{arg} must be one of {KV_DTYPES}, got {dtype!r}")
+
+    def _buffers(self):
+        return ("data",) if self.scales is None else ("data", "scales")
+
+    def reserve(self, rows: int, used: int) -> None:
+        """Capacity for rows rows (geometric growth), keeping the first used."""
+        if rows <= self.data.shape[0]:
+            return
+        cap = max(rows, 2 * self.data.shape[0])
+        for name in self._buffers():
+            old = getattr(self, name)
+            grown = torch.empty(cap, old.shape[1], device=self.device, dtype=old.dtype)
+            grown[:used].copy_(old[:used])
+            setattr(self, name, grown)
+
+    def write(self, at: int, src: torch.Tensor, frames, T: int) -> None:
+        """Store the first frames[b] rows of each clip b of src (bf16 [B·T, 2·dim], clip b at rows b·T ..)
+        from row at on, back to back; reserve first."""
+        parts = (src,) if self.scales is None else ops.mx8_quant(src)
+        for part, name in zip(parts, self._buffers()):
+            dst = getattr(self, name)
+            if all(n == T for n in frames):
+                dst[at:at + len(frames) * T].copy_(part)
+            else:
+                row = at
+                for b, n in enumerate(frames):
+                    dst[row:row + n].copy_(part[b * T:b * T + n])
+                    row += n
+
+    def rows(self, a: int, b: int) -> torch.Tensor:
+        """Rows a .. b-1 as bf16: a view for "bf16", what the stored bytes mean (ops.mx8_dequant) for "mx8"."""
+        if self.scales is None:
+            return self.data[a:b]
+        return ops.mx8_dequant(self.data[a:b], self.scales[a:b])
+
+    def xattn_operands(self):
+        """k, v, {ks, vs}: the column views ops.xattn_seg_fwd attends over in place."""
+        P = self.data.shape[1] // 2
+        scales = {} if self.scales is None else dict(ks=self.scales[:, :P // 32], vs=self.scales[:, P // 32:])
+        return self.data[:, :P], self.data[:, P:], scales
+
+    def align_operands(self):
+        """kv, {scales}: what ops.align_matrix_seg_fwd reads in place."""
+        return self.data, ({} if self.scales is None else dict(scales=self.scales))
 
 
 def kv_bytes_per_frame(dim: int, kv_dtype: str = "bf16") -> int:
     """Bytes an AudioStateStore of projection width dim holds per stored frame (one K|V row of 2·dim
-    columns): "bf16" 4·dim (3,072 at dim = 768); "mx8" 2·dim e4m3 bytes + 2·dim/32 E8M0 scale bytes
-    (1,584 at dim = 768, 0.516 of bf16)."""
-    if kv_dtype == "bf16":
-        return 4 * dim
-    if kv_dtype == "mx8":
-        return 2 * dim + 2 * dim // 32
-    raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
-
-
-ALIGN_MAX_FRAMES = 2048   # the T limit of ste_align_matrix_seg_fwd and ste_align_decode
+    columns), RowBank.bytes_per_frame: 3,072 at dim = 768 for "bf16", 1,584 for "mx8"."""
+    return RowBank.bytes_per_frame(dim, kv_dtype, "kv_dtype")
 
 
 def align_bytes_per_frame(dim: int, align_dtype: str = "bf16") -> int:
     """Bytes an AudioStateStore(align_rows=True) of projection width dim adds per stored frame, whatever
-    kv_dtype is: one K|V row of the alignment head, 2·dim columns.  "bf16" 4·dim bytes (3,072 at
-    dim = 768); "mx8" 2·dim e4m3 bytes + 2·dim/32 E8M0 scale bytes (1,584 at dim = 768)."""
-    if align_dtype == "bf16":
-        return 4 * dim
-    if align_dtype == "mx8":
-        return 2 * dim + 2 * dim // 32
-    raise ValueError(f"align_dtype must be one of {KV_DTYPES}, got {align_dtype!r}")
+    kv_dtype is: one K|V row of the alignment head, RowBank.bytes_per_frame."""
+    return RowBank.bytes_per_frame(dim, align_dtype, "align_dtype")
 
 
 class AudioStateStore:
@@ -299,7 +363,8 @@ class AudioStateStore:
               ste_align_matrix_seg_mx8_fwd reads the bytes in place.  Needs P % 64 == 0, else
               ValueError.
     Without align_rows the argument has no effect.  align_kv_rows(n) says what clip n's stored rows
-    mean, as bf16, for either.
+    mean, as bf16, for either.  Both sets of rows are RowBanks, kv_bank and align_bank; kv / kv_scales
+    and akv / akv_scales are their tensors.
 
     The store is valid for the weights it was built with: it records the model's
     ParamStore.weights_token() at the first add, and adding to or scoring against it after the
@@ -310,34 +375,15 @@ class AudioStateStore:
         self.model, self.device = model, torch.device(device)
         self.dim = int(model.projection_dim)
         self.fused = bool(getattr(model, "use_cross_modal", False))
-        if kv_dtype not in KV_DTYPES:
-            raise ValueError(f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
-        if kv_dtype == "mx8" and self.fused and self.dim % 64:
-            raise ValueError(f'kv_dtype="mx8" needs projection_dim % 64 == 0 (MX blocks of 32 over the 2P columns, '
-                             f"quantised 128 at a time), got {self.dim}")
-        self.kv_dtype = kv_dtype
+        self.kv_dtype, self.align_dtype = kv_dtype, align_dtype
         self.align_rows = bool(align_rows)
+        cap = int(reserve_frames)
+        self.kv_bank = RowBank(self.dim, kv_dtype, cap, self.device, arg="kv_dtype", held=self.fused)
         if self.align_rows and not getattr(model, "use_word_alignment", False):
             raise ValueError("align_rows=True needs a model built with use_word_alignment=True")
-        if align_dtype not in KV_DTYPES:
-            raise ValueError(f"align_dtype must be one of {KV_DTYPES}, got {align_dtype!r}")
-        if align_dtype == "mx8" and self.align_rows and self.dim % 64:
-            raise ValueError(f'align_dtype="mx8" needs projection_dim % 64 == 0 (MX blocks of 32 over the 2P '
-                             f"columns, quantised 128 at a time), got {self.dim}")
-        self.align_dtype = align_dtype
-        self.index = EmbeddingIndex(self.dim, index_dtype, self.device)
-        cap = max(int(reserve_frames), 0) if self.fused else 0
-        mx8 = kv_dtype == "mx8"
-        self.kv = torch.empty(cap, 2 * self.dim, device=self.device, dtype=torch.uint8 if mx8 else BF16)
-        # the E8M0 block scales of kv's rows (mx8 only): grown together with kv
-        self.kv_scales = torch.empty(cap, 2 * self.dim // 32, device=self.device, dtype=torch.uint8) if mx8 else None
         # the alignment head's K|V rows (align_rows only), numbered as kv's rows are
-        amx8 = self.align_rows and align_dtype == "mx8"
-        acap = max(int(reserve_frames), 0)
-        self.akv = torch.empty(acap, 2 * self.dim, device=self.device, dtype=torch.uint8 if amx8 else BF16) \
-            if self.align_rows else None
-        # the E8M0 block scales of akv's rows (align_dtype "mx8" only): grown together with akv
-        self.akv_scales = torch.empty(acap, 2 * self.dim // 32, device=self.device, dtype=torch.uint8) if amx8 else None
+        self.align_bank = RowBank(self.dim, align_dtype, cap, self.device, arg="align_dtype", held=self.align_rows)
+        self.index = EmbeddingIndex(self.dim, index_dtype, self.device)
         self.rows = 0                         # rows of kv / akv in use
         self._seg_row: list[int] = []
         self._seg_len: list[int] = []
@@ -353,31 +399,31 @@ class AudioStateStore:
         if self._token is not None and self._token != self.model.store.weights_token():
             raise RuntimeError("the AudioStateStore was built with other weights: rebuild it after a weight update")
 
-    def _reserve_align(self, rows: int) -> None:
-        if rows <= self.akv.shape[0]:
-            return
-        cap = max(rows, 2 * self.akv.shape[0])
-        grown = torch.empty(cap, self.akv.shape[1], device=self.device, dtype=self.akv.dtype)
-        grown[:self.rows].copy_(self.akv[:self.rows])
-        self.akv = grown
-        if self.akv_scales is not None:
-            grown = torch.empty(cap, self.akv_scales.shape[1], device=self.device, dtype=torch.uint8)
-            grown[:self.rows].copy_(self.akv_scales[:self.rows])
-            self.akv_scales = grown
+    @property
+    def kv(self) -> torch.Tensor:
+        """The K|V rows' buffer [capacity, 2P] (empty without use_cross_modal)."""
+        return self.kv_bank.data
+
+    @property
+    def kv_scales(self):
+        """The E8M0 block scales of kv's rows (kv_dtype "mx8" only, else None)."""
+        return self.kv_bank.scales
+
+    @property
+    def akv(self):
+        """The alignment head's K|V rows [capacity, 2P] (align_rows only, else None)."""
+        return self.align_bank.data if self.align_rows else None
+
+    @property
+    def akv_scales(self):
+        """The E8M0 block scales of akv's rows (align_rows with align_dtype "mx8" only, else None)."""
+        return self.align_bank.scales if self.align_rows else None
 
     def _reserve(self, rows: int) -> None:
         if self.align_rows:
-            self._reserve_align(rows)
-        if not self.fused or rows <= self.kv.shape[0]:
-            return
-        cap = max(rows, 2 * self.kv.shape[0])
-        grown = torch.empty(cap, self.kv.shape[1], device=self.device, dtype=self.kv.dtype)
-        grown[:self.rows].copy_(self.kv[:self.rows])
-        self.kv = grown
-        if self.kv_scales is not None:
-            grown = torch.empty(cap, self.kv_scales.shape[1], device=self.device, dtype=torch.uint8)
-            grown[:self.rows].copy_(self.kv_scales[:self.rows])
-            self.kv_scales = grown
+            self.align_bank.reserve(rows, self.rows)
+        if self.fused:
+            self.kv_bank.reserve(rows, self.rows)
 
     @torch.no_grad()
     def add(self, input_values, attention_mask_audio=None, *, audio_encoded=None) -> None:
@@ -387,19 +433,11 @@ class AudioStateStore:
         model, eng = self.model, self.model.engine
         self.check()
         if audio_encoded is None:
-            was_training, model.training = model.training, False   # encode_audio reads the flag: no dropout here
-            try:
+            with model._eval_arithmetic():
                 audio_encoded = model.encode_audio(input_values, attention_mask_audio)
-            finally:
-                model.training = was_training
         aproj, ah = audio_encoded
         B, T, Ha = ah.shape
-        am = attention_mask_audio
-        if am is not None and eng.raw_audio and am.shape[-1] != T:
-            from .wav2vec2 import frame_mask   # a sample-level wav2vec2 mask, as in score_pairs
-            am32 = frame_mask(eng.acfg, am, B, am.shape[-1], T, self.device)[1]
-        else:
-            am32 = eng._mask32(am.to(self.device, torch.int64), B * T) if am is not None else None
+        am32 = eng._frame_mask32(attention_mask_audio, B, T)
         if am32 is None:
             frames = [T] * B
         else:
@@ -416,24 +454,15 @@ class AudioStateStore:
             ahb = ops.cast_bf16(ah.reshape(B * T, Ha).float().contiguous(),
                                 torch.empty(B * T, Ha, device=self.device, dtype=BF16))
             self._reserve(self.rows + sum(frames))
-            pairs = []   # (source, destination): the bf16 rows, or their e4m3 bytes and E8M0 scales
             if self.fused:
                 kv = eng._kv("text_to_audio_attention", "audio_seq_to_projection", ahb)[0]
-                pairs = [(kv, self.kv)] if self.kv_scales is None \
-                    else list(zip(ops.mx8_quant(kv), (self.kv, self.kv_scales)))
             if self.align_rows:
                 from .align import audio_kv
                 akv = audio_kv(eng, ahb)
-                pairs += [(akv, self.akv)] if self.akv_scales is None \
-                    else list(zip(ops.mx8_quant(akv), (self.akv, self.akv_scales)))
-            for src, dst in pairs:
-                if all(n == T for n in frames):
-                    dst[self.rows:self.rows + B * T].copy_(src)
-                else:
-                    at = self.rows
-                    for b, n in enumerate(frames):
-                        dst[at:at + n].copy_(src[b * T:b * T + n])
-                        at += n
+            if self.fused:                     # both projections first, then the copies, bank by bank
+                self.kv_bank.write(self.rows, kv, frames, T)
+            if self.align_rows:
+                self.align_bank.write(self.rows, akv, frames, T)
         for n in frames:
             self._seg_row.append(self.rows)
             self._seg_len.append(n)
@@ -481,22 +510,14 @@ class AudioStateStore:
         stored bytes mean (ops.mx8_dequant) for "mx8"."""
         if not self.fused:
             raise ValueError("the store keeps no K/V rows without use_cross_modal")
-        a = self._seg_row[n]
-        b = a + self._seg_len[n]
-        if self.kv_scales is None:
-            return self.kv[a:b]
-        return ops.mx8_dequant(self.kv[a:b], self.kv_scales[a:b])
+        return self.kv_bank.rows(self._seg_row[n], self._seg_row[n] + self._seg_len[n])
 
     def align_kv_rows(self, n: int) -> torch.Tensor:
         """Clip n's stored alignment-head K|V rows as bf16 [frames, 2P]: a slice of akv for "bf16" (a
         view), what the stored bytes mean (ops.mx8_dequant) for "mx8"."""
         if not self.align_rows:
             raise ValueError("the store keeps no alignment rows without align_rows=True")
-        a = self._seg_row[n]
-        b = a + self._seg_len[n]
-        if self.akv_scales is None:
-            return self.akv[a:b]
-        return ops.mx8_dequant(self.akv[a:b], self.akv_scales[a:b])
+        return self.align_bank.rows(self._seg_row[n], self._seg_row[n] + self._seg_len[n])
 
     def search(self, text_emb: torch.Tensor, k: int):
         """Stage 1: (values fp32 [Q, k], indices int32 [Q, k]) of the k best clips per unit text row,
@@ -525,11 +546,8 @@ def search_clips(model, store, input_ids, attention_mask, k, *, rerank=True, loc
     with free_ends=True the phrase is located as a fragment of what each hit says."""
     if attention_mask is None:
         attention_mask = torch.ones_like(input_ids)
-    was_training, model.training = model.training, False   # encode_text reads the flag: no dropout here
-    try:
+    with model._eval_arithmetic():
         enc = model.encode_text(input_ids, attention_mask)
-    finally:
-        model.training = was_training
     vals, idx = store.search(_unit_rows(enc[0]), k)
     if rerank and getattr(model, "use_cross_modal", False):
         vals, idx = rerank_clips(model, input_ids, attention_mask, store, idx, text_encoded=enc)

@@ -64,6 +64,10 @@ def _bf16(t: Tensor) -> Tensor:
     return ops.cast_bf16(t, torch.empty(t.shape, device=t.device, dtype=BF16))
 
 
+def _i32(t: Tensor) -> Tensor:
+    return t.reshape(-1).to(torch.int32).contiguous()
+
+
 # ------------------------------------------------------------------------ fbank
 @torch.library.custom_op("ste::fbank", mutates_args=())
 def fbank(wav: Tensor, lengths: Tensor, t_max: int, pad_value: float = 1.0, mask_mode: int = 0) -> tuple[Tensor, Tensor]:
@@ -316,6 +320,16 @@ def _xattn_mq_fake(q, qrow, k, v, mask, C, nh):
     return q.new_empty(qrow.numel(), q.shape[-1], dtype=F32)
 
 
+def _xattn_seg(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, nh, ks=None, vs=None):
+    """The body of ste::xattn_seg (no scales: k / v to bf16) and ste::xattn_seg_mx8 (k / v as given)."""
+    out = torch.empty(qrow.numel(), q.shape[-1], device=q.device, dtype=F32)
+    rows = _bf16 if ks is None else (lambda t: t)
+    ops.xattn_seg_fwd(q.float().contiguous(), _i32(qrow), _i32(pseg), rows(k), rows(v),
+                      seg_row.reshape(-1).to(torch.int64).contiguous(), _i32(seg_len), _i32(tile_first),
+                      _i32(tile_cnt), int(nh), out, ks=ks, vs=vs)
+    return out
+
+
 @torch.library.custom_op("ste::xattn_seg", mutates_args=())
 def xattn_seg(q: Tensor, qrow: Tensor, pseg: Tensor, k: Tensor, v: Tensor, seg_row: Tensor, seg_len: Tensor,
               tile_first: Tensor, tile_cnt: Tensor, nh: int) -> Tensor:
@@ -323,15 +337,7 @@ def xattn_seg(q: Tensor, qrow: Tensor, pseg: Tensor, k: Tensor, v: Tensor, seg_r
     pseg int [R] (sorted by segment, -1 = empty pair -> zero row), k / v [rows, P] (bf16, or fp32 cast
     to bf16), seg_row int64 [G] / seg_len int [G] (first row and length of a segment), tile_first /
     tile_cnt int [tiles] (retrieval.plan_clip_pairs) -> out fp32 [R, P]."""
-    out = torch.empty(qrow.numel(), q.shape[-1], device=q.device, dtype=F32)
-
-    def i32(t):
-        return t.reshape(-1).to(torch.int32).contiguous()
-
-    ops.xattn_seg_fwd(q.float().contiguous(), i32(qrow), i32(pseg), _bf16(k), _bf16(v),
-                      seg_row.reshape(-1).to(torch.int64).contiguous(), i32(seg_len), i32(tile_first), i32(tile_cnt),
-                      int(nh), out)
-    return out
+    return _xattn_seg(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, nh)
 
 
 @xattn_seg.register_fake
@@ -346,15 +352,7 @@ def xattn_seg_mx8(q: Tensor, qrow: Tensor, pseg: Tensor, k: Tensor, v: Tensor, k
     buffer), ks / vs uint8 [rows, P/32] (their E8M0 block scales, views of one buffer); the other
     operands and out fp32 [R, P] as ste::xattn_seg.  The same bits as ste::xattn_seg on the dequantised
     rows (ops.mx8_dequant)."""
-    out = torch.empty(qrow.numel(), q.shape[-1], device=q.device, dtype=F32)
-
-    def i32(t):
-        return t.reshape(-1).to(torch.int32).contiguous()
-
-    ops.xattn_seg_mx8_fwd(q.float().contiguous(), i32(qrow), i32(pseg), k, v, ks, vs,
-                          seg_row.reshape(-1).to(torch.int64).contiguous(), i32(seg_len), i32(tile_first),
-                          i32(tile_cnt), int(nh), out)
-    return out
+    return _xattn_seg(q, qrow, pseg, k, v, seg_row, seg_len, tile_first, tile_cnt, nh, ks=ks, vs=vs)
 
 
 @xattn_seg_mx8.register_fake
@@ -389,6 +387,19 @@ def _align_matrix_fake(q, kv, kmask, nh):
     return (q.new_empty(B, L, T, dtype=F32), q.new_empty(B, T, L, dtype=F32), q.new_empty(B, L, P, dtype=BF16))
 
 
+def _align_matrix_seg(q, qblk, pseg, kv, seg_row, seg_len, Tmax, nh, scales=None):
+    """The body of ste::align_matrix_seg (no scales: kv to bf16) and ste::align_matrix_seg_mx8 (kv as given)."""
+    U, L, P = q.shape
+    R, Tmax = qblk.numel(), int(Tmax)
+    matrix = torch.zeros(R, L, Tmax, device=q.device, dtype=F32)
+    emit = torch.full((R, Tmax, L), float("-inf"), device=q.device, dtype=F32)
+    out = torch.empty(R * L, P, device=q.device, dtype=BF16)
+    ops.align_matrix_seg_fwd(_bf16(q.reshape(U * L, P)), _i32(qblk), _i32(pseg), _bf16(kv) if scales is None else kv,
+                             seg_row.reshape(-1).to(torch.int64).contiguous(), _i32(seg_len), L, Tmax, int(nh),
+                             scales=scales, matrix=matrix, emit=emit, out=out)
+    return matrix, emit, out.view(R, L, P)
+
+
 @torch.library.custom_op("ste::align_matrix_seg", mutates_args=())
 def align_matrix_seg(q: Tensor, qblk: Tensor, pseg: Tensor, kv: Tensor, seg_row: Tensor, seg_len: Tensor, Tmax: int,
                      nh: int) -> tuple[Tensor, Tensor, Tensor]:
@@ -398,21 +409,10 @@ def align_matrix_seg(q: Tensor, qblk: Tensor, pseg: Tensor, kv: Tensor, seg_row:
     of a segment), Tmax >= the pairs' segment lengths -> (matrix fp32 [R, L, Tmax], emit fp32
     [R, Tmax, L], out bf16 [R, L, P]).  A pair with F frames fills frames [:F]; the frames beyond,
     and an empty pair's, are 0 in matrix and -inf in emit."""
-    U, L, P = q.shape
-    R, Tmax = qblk.numel(), int(Tmax)
+    P = q.shape[2]
     if kv.dim() != 2 or kv.shape[1] != 2 * P:
         raise ValueError(f"align_matrix_seg: q {tuple(q.shape)}, kv {tuple(kv.shape)}")
-    matrix = torch.zeros(R, L, Tmax, device=q.device, dtype=F32)
-    emit = torch.full((R, Tmax, L), float("-inf"), device=q.device, dtype=F32)
-    out = torch.empty(R * L, P, device=q.device, dtype=BF16)
-
-    def i32(t):
-        return t.reshape(-1).to(torch.int32).contiguous()
-
-    ops.align_matrix_seg_fwd(_bf16(q.reshape(U * L, P)), i32(qblk), i32(pseg), _bf16(kv),
-                             seg_row.reshape(-1).to(torch.int64).contiguous(), i32(seg_len), L, Tmax, int(nh),
-                             matrix=matrix, emit=emit, out=out)
-    return matrix, emit, out.view(R, L, P)
+    return _align_matrix_seg(q, qblk, pseg, kv, seg_row, seg_len, Tmax, nh)
 
 
 @align_matrix_seg.register_fake
@@ -429,23 +429,12 @@ def align_matrix_seg_mx8(q: Tensor, qblk: Tensor, pseg: Tensor, kv: Tensor, scal
     [rows, 2P/32] (their E8M0 block scales); the other operands and (matrix, emit, out) as
     ste::align_matrix_seg.  The same bits as ste::align_matrix_seg on the dequantised rows
     (ops.mx8_dequant)."""
-    U, L, P = q.shape
-    R, Tmax = qblk.numel(), int(Tmax)
+    P = q.shape[2]
     if (kv.dim() != 2 or kv.shape[1] != 2 * P or kv.dtype != torch.uint8 or scales.dtype != torch.uint8
             or scales.shape != (kv.shape[0], 2 * P // 32)):
         raise ValueError(f"align_matrix_seg_mx8: q {tuple(q.shape)}, kv {tuple(kv.shape)} {kv.dtype}, "
                          f"scales {tuple(scales.shape)} {scales.dtype}")
-    matrix = torch.zeros(R, L, Tmax, device=q.device, dtype=F32)
-    emit = torch.full((R, Tmax, L), float("-inf"), device=q.device, dtype=F32)
-    out = torch.empty(R * L, P, device=q.device, dtype=BF16)
-
-    def i32(t):
-        return t.reshape(-1).to(torch.int32).contiguous()
-
-    ops.align_matrix_seg_mx8_fwd(_bf16(q.reshape(U * L, P)), i32(qblk), i32(pseg), kv, scales,
-                                 seg_row.reshape(-1).to(torch.int64).contiguous(), i32(seg_len), L, Tmax, int(nh),
-                                 matrix=matrix, emit=emit, out=out)
-    return matrix, emit, out.view(R, L, P)
+    return _align_matrix_seg(q, qblk, pseg, kv, seg_row, seg_len, Tmax, nh, scales=scales)
 
 
 @align_matrix_seg_mx8.register_fake

@@ -35,9 +35,9 @@ def test_names_are_exported():
     sig = inspect.signature(ste.AudioStateStore.__init__)
     assert sig.parameters["align_dtype"].default == "bf16"
     assert sig.parameters["align_rows"].default is False and sig.parameters["kv_dtype"].default == "bf16"
-    assert callable(ops.align_matrix_seg_mx8_fwd)
-    names = list(inspect.signature(ops.align_matrix_seg_mx8_fwd).parameters)
-    assert names == ["q", "qblk", "pseg", "kv", "scales", "seg_row", "seg_len", "L", "Tmax", "nh", "matrix", "emit",
+    assert callable(ops.align_matrix_seg_fwd)              # one entry for both row dtypes: scales= selects MX-fp8
+    names = list(inspect.signature(ops.align_matrix_seg_fwd).parameters)
+    assert names == ["q", "qblk", "pseg", "kv", "seg_row", "seg_len", "L", "Tmax", "nh", "scales", "matrix", "emit",
                      "out"]
     # the callers gain no argument
     assert "align_dtype" not in inspect.signature(ste.search_clips).parameters

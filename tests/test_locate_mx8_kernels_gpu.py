@@ -123,8 +123,8 @@ def _big(L, P, nh):
     slen = torch.tensor(FS, dtype=I32, device=DEV)
     kv, sc = kvb[:, :2 * P], scb[:, :2 * P // 32]
     matrix, emit, out = _outputs(R, L, Tmax, P)
-    ops.align_matrix_seg_mx8_fwd(qbuf[:, :P], qblk, pseg, kv, sc, srow, slen, L, Tmax, nh, matrix=matrix,
-                                 emit=emit[:, :, :L], out=out[:, :P])
+    ops.align_matrix_seg_fwd(qbuf[:, :P], qblk, pseg, kv, srow, slen, L, Tmax, nh, scales=sc, matrix=matrix,
+                             emit=emit[:, :, :L], out=out[:, :P])
     wm, we, wo = _outputs(R, L, Tmax, P)
     ops.align_matrix_seg_fwd(qbuf[:, :P], qblk, pseg, deq[:, :2 * P], srow, slen, L, Tmax, nh, matrix=wm,
                              emit=we[:, :, :L], out=wo[:, :P])
@@ -189,7 +189,7 @@ def test_the_rounding_corner_of_the_value_element(ops):
     got = torch.full((L, P), NAN, device=DEV, dtype=BF16)
     want = torch.full((L, P), NAN, device=DEV, dtype=BF16)
     gm, wm = torch.full((1, L, F), NAN, device=DEV), torch.full((1, L, F), NAN, device=DEV)
-    ops.align_matrix_seg_mx8_fwd(qu, one(0), one(0), q8, s8, one(0, I64), one(F), L, F, nh, matrix=gm, out=got)
+    ops.align_matrix_seg_fwd(qu, one(0), one(0), q8, one(0, I64), one(F), L, F, nh, scales=s8, matrix=gm, out=got)
     ops.align_matrix_seg_fwd(qu, one(0), one(0), deq, one(0, I64), one(F), L, F, nh, matrix=wm, out=want)
     assert torch.equal(gm, wm) and float(gm.min()) > 0.0       # every frame carries weight in the sums
     assert torch.equal(_bits(got), _bits(want))                # (E = 254 overflows to inf: bits, not values)
@@ -215,8 +215,8 @@ def test_a_pair_does_not_depend_on_its_launch(ops):
             m = torch.full((1, L, F), NAN, device=DEV) if which in ("all", "matrix") else None
             e = torch.full((1, F, L), NAN, device=DEV) if which in ("all", "emit") else None
             o = torch.full((L, P), NAN, device=DEV, dtype=BF16) if which in ("all", "out") else None
-            ops.align_matrix_seg_mx8_fwd(q1, one(u), one(0), kv1, sc1, one(0, I64), one(F), L, F, nh, matrix=m, emit=e,
-                                         out=o)
+            ops.align_matrix_seg_fwd(q1, one(u), one(0), kv1, one(0, I64), one(F), L, F, nh, scales=sc1, matrix=m,
+                                     emit=e, out=o)
             for got, ref in zip((m, e, o), want):
                 if got is not None:
                     assert torch.equal(got.view(ref.shape), ref), (g, which)
@@ -226,8 +226,8 @@ def test_a_pair_does_not_depend_on_its_launch(ops):
         m = torch.full((5, L, Tmax), NAN, device=DEV)
         e = torch.full((5, Tmax, L), NAN, device=DEV)
         o = torch.full((5 * L, P), NAN, device=DEV, dtype=BF16)
-        ops.align_matrix_seg_mx8_fwd(b["q"][:, :P], qb, ps, b["kv"], b["sc"], b["srow"], b["slen"], L, Tmax, nh,
-                                     matrix=m, emit=e, out=o)
+        ops.align_matrix_seg_fwd(b["q"][:, :P], qb, ps, b["kv"], b["srow"], b["slen"], L, Tmax, nh, scales=b["sc"],
+                                 matrix=m, emit=e, out=o)
         assert torch.equal(m[4, :, :F], want[0]) and torch.equal(e[4, :F], want[1]) and torch.equal(o[4 * L:], want[2])
         assert bool(m[4, :, F:].isnan().all()) and bool(e[4, F:].isnan().all())
         assert bool(m[1].isnan().all()) and float(o[L:2 * L].float().abs().max()) == 0.0
@@ -254,8 +254,8 @@ def test_empty_pairs(ops):
                 torch.full((R * L, P), NAN, device=DEV, dtype=BF16))
 
     m, e, o = outs()
-    ops.align_matrix_seg_mx8_fwd(q, qb, ps, kvb[:, :2 * P], scb[:, :2 * P // 32], srow, slen, L, Tmax, nh, matrix=m,
-                                 emit=e, out=o)
+    ops.align_matrix_seg_fwd(q, qb, ps, kvb[:, :2 * P], srow, slen, L, Tmax, nh, scales=scb[:, :2 * P // 32], matrix=m,
+                             emit=e, out=o)
     wm, we, wo = outs()
     ops.align_matrix_seg_fwd(q, qb, ps, deq[:, :2 * P], srow, slen, L, Tmax, nh, matrix=wm, emit=we, out=wo)
     for r in range(5):
@@ -268,7 +268,7 @@ def test_empty_pairs(ops):
         assert torch.equal(_bits(got), _bits(want))
     # without out nothing at all is written for an empty pair
     m2 = torch.full((R, L, Tmax), NAN, device=DEV)
-    ops.align_matrix_seg_mx8_fwd(q, qb, ps, kvb[:, :2 * P], scb[:, :2 * P // 32], srow, slen, L, Tmax, nh, matrix=m2)
+    ops.align_matrix_seg_fwd(q, qb, ps, kvb[:, :2 * P], srow, slen, L, Tmax, nh, scales=scb[:, :2 * P // 32], matrix=m2)
     assert bool(m2[:5].isnan().all()) and torch.equal(m2[5, :, :5], m[5, :, :5])
 
 
@@ -332,9 +332,9 @@ def test_planted_paths_come_back(ops):
     qb = torch.tensor([p[0] for p in pairs], dtype=I32, device=DEV)
     ps = torch.tensor([p[1] for p in pairs], dtype=I32, device=DEV)
     emit = torch.full((R, Tmax, L), NAN, device=DEV)
-    ops.align_matrix_seg_mx8_fwd(q, qb, ps, kvb[:, :2 * P], scb[:, :2 * P // 32],
-                                 torch.tensor(seg_row, dtype=I64, device=DEV),
-                                 torch.tensor(lengths, dtype=I32, device=DEV), L, Tmax, nh, emit=emit)
+    ops.align_matrix_seg_fwd(q, qb, ps, kvb[:, :2 * P], torch.tensor(seg_row, dtype=I64, device=DEV),
+                             torch.tensor(lengths, dtype=I32, device=DEV), L, Tmax, nh, scales=scb[:, :2 * P // 32],
+                             emit=emit)
     ntok = torch.tensor([ntoks[u] for u, _ in pairs], dtype=I32, device=DEV)
     nfrm = torch.tensor([lengths[g] for _, g in pairs], dtype=I32, device=DEV)
     spans, score = ops.align_decode(emit, ntok, nfrm)

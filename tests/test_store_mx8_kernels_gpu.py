@@ -87,7 +87,7 @@ def _run(ops, q, buf, seg_row, seg_len, qsel, psel, nh, sc=None, via_op=False):
         out = (torch.ops.ste.xattn_seg if sc is None else torch.ops.ste.xattn_seg_mx8)(*head, *tail, nh)
     else:
         out = torch.full((len(psel), P), float("nan"), device=DEV)
-        (ops.xattn_seg_fwd if sc is None else ops.xattn_seg_mx8_fwd)(*head, *tail, nh, out)
+        ops.xattn_seg_fwd(*head[:5], *tail, nh, out, **dict(zip(("ks", "vs"), head[5:])))
     torch.cuda.synchronize()
     return out.index_select(0, plan["inverse"].view(-1).to(DEV))
 
@@ -257,10 +257,10 @@ def test_shape_errors_launch_nothing(ops):
         flat = torch.full((max(R, 1) * P,), 7.0, device=DEV)
         i32 = lambda v: torch.tensor(v, dtype=torch.int32, device=DEV)            # noqa: E731
         with pytest.raises(SteError):
-            ops.xattn_seg_mx8_fwd(q, i32([0] * R), i32([0] * R), kv[:, koff:koff + P], kv[:, koff + P:koff + 2 * P],
-                                  sc[:, :P // 32 + 1], sc[:, P // 32 + 1:],
-                                  torch.tensor([0] * G, dtype=torch.int64, device=DEV), i32([8] * G), i32([0] * ntile),
-                                  i32([R] * ntile), nh, flat[:R * P].view(R, P))
+            ops.xattn_seg_fwd(q, i32([0] * R), i32([0] * R), kv[:, koff:koff + P], kv[:, koff + P:koff + 2 * P],
+                              torch.tensor([0] * G, dtype=torch.int64, device=DEV), i32([8] * G), i32([0] * ntile),
+                              i32([R] * ntile), nh, flat[:R * P].view(R, P), ks=sc[:, :P // 32 + 1],
+                              vs=sc[:, P // 32 + 1:])
         torch.cuda.synchronize()
         assert torch.equal(flat, torch.full_like(flat, 7.0)), "out is untouched"
 
