@@ -410,6 +410,29 @@ int ste_attn_pool_fwd_f32(const float* t, const float* w2, const float* b2, cons
 int ste_attn_pool_bwd_f32(const float* t, const float* w2, const float* h, const float* weights, const float* dpooled,
                           const int32_t* mask, int B, int L, int Hh, int H, float* dh, float* dt, float* dw2,
                           float* db2, float* db1, float* work, void* stream);
+/* Segmented attentive pooling, forward only: the same pooling of G segments of ONE row
+ * buffer.  t [rows, Hh] is the scorer's tanh output and h [rows, H] the hidden states of the buffer
+ * (bf16 for ste_attn_pool_seg_fwd, fp32 for ste_attn_pool_seg_fwd_f32); segment g is rows
+ * seg_row[g] .. seg_row[g] + seg_len[g] - 1 (seg_row int64 [G], seg_len int32 [G], on the device).
+ * Segments may overlap, repeat and come in any order: the windows of a long recording are views of
+ * rows that are stored once.  Three launches, no atomics, no memset, 64-bit row addresses:
+ *   score[r] = t_r·w2 + b2, once per row of the buffer (fp32 [rows], written);
+ *   stat[g] = (max, 1/Σ exp) over segment g's scores (fp32 [G, 2], written);
+ *   pooled[g] = Σ_l exp(score_l - max)·inv · h_l (fp32 [G, H], and bf16 [G, H] if pooled_bf16).
+ * Contract: pooled[g] is bit-identical to ste_attn_pool_fwd[_f32](B = 1, L = seg_len[g], mask = NULL)
+ * on a copy of the segment's rows, whatever G, the segment's position, its overlaps and the other
+ * segments are: both run the device code of csrc/attn_pool.h, whose per-thread shares depend on a
+ * row's index inside its segment alone and whose reductions have a fixed order.
+ * A segment with seg_len <= 0, seg_len > 8192, seg_row < 0 or seg_row + seg_len > rows is empty: its
+ * pooled row (and the bf16 copy) is zeros and no row of t or h is read for it.
+ * STE_ERR_SHAPE before any launch for G < 1, rows < 1, Hh or H no positive multiple of 4;
+ * STE_ERR_ARG for a NULL pointer other than pooled_bf16. */
+int ste_attn_pool_seg_fwd(const void* t, const float* w2, const float* b2, const void* h, int64_t rows,
+                          const int64_t* seg_row, const int32_t* seg_len, int G, int Hh, int H, float* score,
+                          float* stat, float* pooled, void* pooled_bf16, void* stream);
+int ste_attn_pool_seg_fwd_f32(const float* t, const float* w2, const float* b2, const float* h, int64_t rows,
+                              const int64_t* seg_row, const int32_t* seg_len, int G, int Hh, int H, float* score,
+                              float* stat, float* pooled, void* pooled_bf16, void* stream);
 
 /* Pooling without the scorer, use_attentive_pooling=False
  * (ref:training/trainer_unfreeze.py:578-580 text `last_hidden_state[:, 0, :]`, :621-636 audio

@@ -6,6 +6,7 @@
 // These are small (rows = batch), latency-bound kernels; the big sequence-length
 // projections around them run through ste_gemm.
 #include "common.h"
+#include "attn_pool.h"
 #include "xattn_fwd.h"
 #include "../../include/ste.h"
 
@@ -14,45 +15,6 @@ namespace {
 constexpr int NT = 256;
 static_assert(NT == XATTN_NT, "ste_xattn_fwd launches xattn_fwd_kernel with NT threads");
 
-STE_DEV float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float s = 0.f;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += red[i];
-  return s;
-}
-STE_DEV float block_max(float v, float* red) {
-  v = wave_max(v);
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float s = -INFINITY;
-  for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s = fmaxf(s, red[i]);
-  return s;
-}
-
-// 4 consecutive elements of a bf16 or fp32 row (the pooling kernels run on the bf16 audio states
-// and on the fp32 text states, see ste_attn_pool_fwd_f32)
-STE_DEV f32x4 ld4(const bf16* p) { return load_bf16x4(p); }
-STE_DEV f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
-STE_DEV void st4(bf16* p, f32x4 v) { store_bf16x4(p, v); }
-STE_DEV void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-
-template <typename T>
-STE_DEV float row_dot(const T* a, const float* b, int n, int lane) {
-  float acc = 0.f;
-  for (int c = lane * 4; c < n; c += 256) {
-    f32x4 x = ld4(a + c);
-    f32x4 y = *reinterpret_cast<const f32x4*>(b + c);
-    acc += x[0] * y[0] + x[1] * y[1] + x[2] * y[2] + x[3] * y[3];
-  }
-  return wave_sum(acc);
-}
-
 // ------------------------------------------------------------ attentive pooling
 // Forward, three launches so the [B*L, H] read is spread over the chip (one block per sample
 // left 3/4 of the CUs idle and walked L rows serially):
@@ -60,8 +22,9 @@ STE_DEV float row_dot(const T* a, const float* b, int n, int lane) {
 //   pool_softmax_kernel w_l = softmax_l(s)                                     grid B
 //   pool_wsum_kernel    pooled[c] = Σ_l w_l h_l[c]: 8 waves split the rows,    grid (B, ceil(H/256))
 //                       partials summed in wave order (deterministic)
-constexpr int POOL_SC_ROWS = 16;
-constexpr int POOL_WS_NT = 512;
+// The device code (block_sum / block_max, ld4 / st4, row_dot and the three bodies) lives in attn_pool.h,
+// shared with attn_pool_seg.hip, whose segments pool to the same bits.
+static_assert(NT == POOL_NT, "the pooling launches use NT threads");
 
 template <typename T>
 __global__ __launch_bounds__(NT) void pool_score_kernel(const T* t, const float* w2, const float* b2,
@@ -69,7 +32,7 @@ __global__ __launch_bounds__(NT) void pool_score_kernel(const T* t, const float*
   const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int l1 = min(L, (int)(blockIdx.y + 1) * POOL_SC_ROWS);
   for (int l = blockIdx.y * POOL_SC_ROWS + w; l < l1; l += NT / 64) {
-    float s = row_dot(t + (int64_t)(b * L + l) * Hh, w2, Hh, lane) + b2[0];
+    float s = pool_score(t + (int64_t)(b * L + l) * Hh, w2, b2, Hh, lane);
     if (mask && mask[b * L + l] == 0) s = -1e9f;
     if (lane == 0) sc[b * L + l] = s;
   }
@@ -78,15 +41,9 @@ __global__ __launch_bounds__(NT) void pool_score_kernel(const T* t, const float*
 __global__ __launch_bounds__(NT) void pool_softmax_kernel(int L, float* sc) {
   __shared__ float red[8];
   float* r = sc + (int64_t)blockIdx.x * L;
-  const int tid = threadIdx.x;
-  float mx = -INFINITY;
-  for (int l = tid; l < L; l += NT) mx = fmaxf(mx, r[l]);
-  mx = block_max(mx, red);
-  float sum = 0.f;
-  for (int l = tid; l < L; l += NT) sum += __expf(r[l] - mx);
-  sum = block_sum(sum, red);
-  const float inv = 1.0f / sum;
-  for (int l = tid; l < L; l += NT) r[l] = __expf(r[l] - mx) * inv;
+  float mx, inv;
+  pool_softmax_stat(r, L, red, mx, inv);
+  for (int l = threadIdx.x; l < L; l += NT) r[l] = pool_weight(r[l], mx, inv);
 }
 
 template <typename T>
@@ -94,26 +51,11 @@ __global__ __launch_bounds__(POOL_WS_NT) void pool_wsum_kernel(const T* h, const
                                                              float* pooled, bf16* pooled_bf16) {
   extern __shared__ float wl[];  // L weights
   __shared__ f32x4 part[POOL_WS_NT / 64][64];
-  constexpr int NW = POOL_WS_NT / 64;
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int b = blockIdx.x, tid = threadIdx.x;
   for (int l = tid; l < L; l += POOL_WS_NT) wl[l] = weights[b * L + l];
   __syncthreads();
-  const int c = blockIdx.y * 256 + lane * 4;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  if (c < H) {
-    const T* hp = h + (int64_t)b * L * H + c;
-#pragma unroll 4
-    for (int l = w; l < L; l += NW) acc += ld4(hp + (int64_t)l * H) * wl[l];
-  }
-  part[w][lane] = acc;
-  __syncthreads();
-  if (w == 0 && c < H) {
-    f32x4 s = part[0][lane];
-#pragma unroll
-    for (int i = 1; i < NW; ++i) s += part[i][lane];
-    *reinterpret_cast<f32x4*>(pooled + (int64_t)b * H + c) = s;
-    if (pooled_bf16) store_bf16x4(pooled_bf16 + (int64_t)b * H + c, s);
-  }
+  pool_wsum_rows(h + (int64_t)b * L * H, wl, L, H, part, pooled + (int64_t)b * H,
+                 pooled_bf16 ? pooled_bf16 + (int64_t)b * H : nullptr);
 }
 
 // Backward, four launches spread over (batch, row chunks) so the [B*L, H] reads fill the chip:
@@ -632,7 +574,7 @@ __global__ __launch_bounds__(NT) void rowmat_f32_kernel(const float* X, int64_t 
 template <typename T>
 static int attn_pool_fwd(const T* t, const float* w2, const float* b2, const T* h, const int32_t* mask, int B, int L,
                          int Hh, int H, float* weights, float* pooled, bf16* pooled_bf16, hipStream_t s) {
-  if (B <= 0 || L <= 0 || (Hh & 3) || (H & 3) || L > 8192) return STE_ERR_SHAPE;
+  if (B <= 0 || L <= 0 || (Hh & 3) || (H & 3) || L > POOL_MAX_L) return STE_ERR_SHAPE;
   hipLaunchKernelGGL(pool_score_kernel<T>, dim3(B, (L + POOL_SC_ROWS - 1) / POOL_SC_ROWS), dim3(NT), 0, s, t, w2, b2,
                      mask, L, Hh, weights);
   STE_CHECK_LAUNCH();

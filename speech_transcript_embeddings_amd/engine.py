@@ -955,6 +955,17 @@ class Engine:
         sv.update(t=t, w=w, h=h if f32 else hb, mask=mask32, f32=f32)
         return pooled
 
+    def _pool_seg_fwd(self, name, h, hs, seg_row, seg_len):
+        """_pool_fwd's attentive pooling for G segments of ONE row buffer: h fp32
+        [rows, H] and its [hi | lo] split image hs, segment g the rows seg_row[g] .. seg_row[g] +
+        seg_len[g] - 1, overlapping freely (the windows of a recording) -> pooled fp32 [G, H].  The
+        scorer Linear runs once over the rows with _pool_fwd's operands; ops.attn_pool_seg_fwd then
+        pools every segment to the bits of the dense kernels on a copy of its rows."""
+        s = self.s
+        t = ops.linear(hs, s.w2(name + ".attention.0.weight"), s.p(name + ".attention.0.bias"), act=ACT_TANH)
+        return ops.attn_pool_seg_fwd(t, s.p(name + ".attention.2.weight").view(-1), s.p(name + ".attention.2.bias"),
+                                     h, seg_row, seg_len)
+
     def _pool_bwd(self, name, sv, dpooled, dh, nb, L):
         s = self.s
         if not self.m.use_attentive_pooling:

@@ -615,6 +615,48 @@ def attn_pool_fwd_f32(t, w2, b2, h, mask, B, L, weights, pooled, pooled_bf16=Non
          ptr(weights), ptr(pooled), ptr(pooled_bf16), _s())
 
 
+def attn_pool_seg_fwd(t, w2, b2, h, seg_row, seg_len, pooled=None, *, pooled_bf16=None):
+    """Attentive pooling of G segments of ONE row buffer (ste_attn_pool_seg_fwd[_f32]):
+    t [rows, Hh] the scorer's tanh output and h [rows, H] the hidden states, both float32 or both
+    bfloat16 (the dtype of h selects the kernel); w2 fp32 [Hh], b2 fp32 [1]; segment g is rows
+    seg_row[g] .. seg_row[g] + seg_len[g] - 1 (seg_row int64 [G], seg_len int32 [G]) and segments may
+    overlap, repeat and come in any order.  -> pooled fp32 [G, H] (written into `pooled` if given; the
+    bf16 copy into pooled_bf16), row g bit-identical to attn_pool_fwd[_f32](B = 1, L = seg_len[g], no
+    mask) on a copy of the segment's rows.  A segment that is empty (seg_len <= 0), longer than 8192
+    rows or not inside the buffer pools to zeros.  ValueError for bad shapes or dtypes."""
+    if t.dim() != 2 or h.dim() != 2 or t.shape[0] != h.shape[0] or h.shape[0] < 1:
+        raise ValueError(f"t and h must be [rows, Hh] and [rows, H] with rows >= 1, got {tuple(t.shape)} and "
+                         f"{tuple(h.shape)}")
+    rows, Hh, H = h.shape[0], t.shape[1], h.shape[1]
+    if Hh < 4 or H < 4 or Hh % 4 or H % 4:
+        raise ValueError(f"Hh and H must be positive multiples of 4, got {Hh} and {H}")
+    if h.dtype not in (F32, BF16) or t.dtype != h.dtype:
+        raise ValueError(f"t and h must both be float32 or both bfloat16, got {t.dtype} and {h.dtype}")
+    if w2.dtype != F32 or b2.dtype != F32 or w2.numel() != Hh or b2.numel() != 1:
+        raise ValueError(f"w2 and b2 must be float32 with {Hh} and 1 elements, got {w2.dtype} {tuple(w2.shape)} and "
+                         f"{b2.dtype} {tuple(b2.shape)}")
+    if seg_row.dtype != torch.int64 or seg_len.dtype != torch.int32:
+        raise ValueError(f"seg_row must be int64 and seg_len int32, got {seg_row.dtype} and {seg_len.dtype}")
+    G = seg_len.numel()
+    if seg_row.dim() != 1 or seg_len.dim() != 1 or seg_row.numel() != G or G < 1:
+        raise ValueError(f"seg_row and seg_len must be [G] with G >= 1, got {tuple(seg_row.shape)} and "
+                         f"{tuple(seg_len.shape)}")
+    for name, o, dt in (("pooled", pooled, F32), ("pooled_bf16", pooled_bf16, BF16)):
+        if o is not None and (o.dtype != dt or o.shape != (G, H) or not o.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} [{G}, {H}], got {o.dtype} {tuple(o.shape)}")
+    if not all(x.is_contiguous() for x in (t, h, w2, b2, seg_row, seg_len)):
+        raise ValueError("attn_pool_seg_fwd takes contiguous operands")
+    if not h.is_cuda or any(x.device != h.device for x in (t, w2, b2, seg_row, seg_len)):
+        raise ValueError("attn_pool_seg_fwd takes operands on one GPU (libste.so has no CPU path)")
+    if pooled is None:
+        pooled = torch.empty(G, H, device=h.device, dtype=F32)
+    score = torch.empty(rows, device=h.device, dtype=F32)
+    stat = torch.empty(G, 2, device=h.device, dtype=F32)
+    call("ste_attn_pool_seg_fwd_f32" if h.dtype == F32 else "ste_attn_pool_seg_fwd", ptr(t), ptr(w2), ptr(b2), ptr(h),
+         rows, ptr(seg_row), ptr(seg_len), G, Hh, H, ptr(score), ptr(stat), ptr(pooled), ptr(pooled_bf16), _s())
+    return pooled
+
+
 def attn_pool_bwd_f32(t, w2, h, weights, dpooled, B, L, dh, dz, dw2=None, db2=None, db1=None, mask=None):
     """attn_pool_bwd on fp32 t / h with an fp32 dz (no low half needed)."""
     assert t.dtype == F32 and h.dtype == F32 and dz.dtype == F32

@@ -34,6 +34,14 @@ of every clip; they are computed once when the corpus is indexed and attended ov
         align_kv_rows(n), align_bytes_per_frame(dim)
     search_clips(model, store, input_ids, attention_mask, k) -> (values, indices, where in each hit)
 
+Recordings of minutes to hours are encoded chunk by chunk, stored once and indexed as
+overlapping windows that are views of the stored rows:
+
+    plan_recording(frames, window, hop, chunk, context) -> the chunks and the windows
+    AudioStateStore.add_recording(features [F, 160]) -> recording id; recording_of, offset_of, recordings
+    best_per_recording(values, idx, recording_of, k) -> each recording's best window, in order
+    search_recordings(model, store, input_ids, attention_mask, k) -> (values, recordings, windows, where)
+
 Scores and selection run in ste_topk_sim (csrc/retrieval.hip): the queries x corpus score matrix
 is never written.  The order is total (value descending, index ascending) and a row's score is
 bit-identical wherever it is computed, so results do not depend on how the corpus was chunked.
@@ -243,6 +251,75 @@ def plan_clip_pairs(idx: torch.Tensor) -> dict:
 
 KV_DTYPES = ("bf16", "mx8")
 ALIGN_MAX_FRAMES = 2048   # the T limit of ste_align_matrix_seg_fwd and ste_align_decode
+POOL_MAX_FRAMES = 8192    # the longest segment ste_attn_pool_seg_fwd pools (and ste_attn_pool_fwd's L limit)
+
+
+# ------------------------------------------------- long recordings
+def plan_recording(frames: int, window_frames: int, hop_frames: int, chunk_frames: int, context_frames: int, *,
+                   max_window: int = POOL_MAX_FRAMES) -> dict:
+    """How a recording of F = frames encoder frames is encoded and indexed (AudioStateStore.add_recording).
+
+    Chunks: the kept ranges [c·chunk, min((c+1)·chunk, F)) partition [0, F); the encoder input of chunk c
+    is its kept range widened by context_frames on both sides and clipped to [0, F), so a kept frame
+    sees at least that much context unless the recording ends sooner.
+
+    Windows: starts 0, hop, 2·hop, ...; one window if F <= window, else ceil((F - window) / hop) + 1;
+    window i has min(window, F - start) frames (only the last can be shorter, and it still has more than
+    window - hop).  Consequence: every span of at most window - hop + 1 frames lies wholly inside some
+    window (the one starting at the last multiple of hop at or before the span, or the last window), which
+    is what lets a free-endpoint locate find a phrase that straddles a window boundary.
+
+    Returns a dict of Python ints and lists: frames; keep and input, the (first, last + 1) ranges of each
+    chunk; window_start and window_len.  ValueError unless 1 <= hop <= window <= max_window (8192, the
+    pooling kernel's segment limit; an align_rows store passes ALIGN_MAX_FRAMES), chunk >= 1,
+    context >= 0 and F >= 1.  Pure Python."""
+    F, W, hop, chunk, ctx = (int(v) for v in (frames, window_frames, hop_frames, chunk_frames, context_frames))
+    if F < 1:
+        raise ValueError(f"a recording has at least one frame, got {F}")
+    if not 1 <= hop <= W <= int(max_window):
+        raise ValueError(f"need 1 <= hop_frames <= window_frames <= {int(max_window)}, got hop_frames={hop}, "
+                         f"window_frames={W}")
+    if chunk < 1 or ctx < 0:
+        raise ValueError(f"need chunk_frames >= 1 and context_frames >= 0, got {chunk} and {ctx}")
+    keep = [(a, min(a + chunk, F)) for a in range(0, F, chunk)]
+    inputs = [(max(a - ctx, 0), min(b + ctx, F)) for a, b in keep]
+    nwin = 1 if F <= W else -(-(F - W) // hop) + 1
+    starts = [i * hop for i in range(nwin)]
+    return dict(frames=F, keep=keep, input=inputs, window_start=starts, window_len=[min(W, F - s) for s in starts])
+
+
+def best_per_recording(values: torch.Tensor, idx: torch.Tensor, recording_of: torch.Tensor, k: int):
+    """Window lists -> recording lists.  values / idx [Q, m]: each query's windows best-first, as
+    store.search or rerank_order return them (-1 = empty slot); recording_of int [N]: the recording of
+    each window.  Keeps, per row and in order, the first (best) window of each recording ->
+    (values fp32 [Q, k], recordings [Q, k], windows [Q, k]), padded with (-inf, -1, -1); k may exceed m or
+    the number of distinct recordings.  Pure torch, any device, no host sync."""
+    idx = torch.as_tensor(idx)
+    if idx.dim() != 2 or values.shape != idx.shape:
+        raise ValueError(f"values and idx must both be [Q, m], got {tuple(values.shape)} and {tuple(idx.shape)}")
+    k = int(k)
+    if k < 1:
+        raise ValueError(f"k must be at least 1, got {k}")
+    Q, m = idx.shape
+    dev = idx.device
+    live = idx >= 0
+    rec = recording_of.to(dev).to(idx.dtype)
+    rec = (torch.where(live, rec[idx.clamp(min=0).long()], torch.full_like(idx, -1)) if rec.numel()
+           else torch.full_like(idx, -1))
+    live = live & (rec >= 0)
+    earlier = torch.ones(m, m, dtype=torch.bool, device=dev).tril(-1)             # [j, j'] with j' < j
+    dup = ((rec.unsqueeze(2) == rec.unsqueeze(1)) & earlier & live.unsqueeze(1)).any(2)
+    keep = live & ~dup
+    order = torch.sort((~keep).to(torch.int8), dim=1, stable=True)[1]             # the kept slots first, in order
+    keep = keep.gather(1, order)
+    vals = torch.where(keep, values.gather(1, order).float(), torch.full((), float("-inf"), device=dev))
+    recs = torch.where(keep, rec.gather(1, order), torch.full_like(idx, -1))
+    wins = torch.where(keep, idx.gather(1, order), torch.full_like(idx, -1))
+    if m < k:
+        pad = (0, k - m)
+        return (torch.nn.functional.pad(vals, pad, value=float("-inf")), torch.nn.functional.pad(recs, pad, value=-1),
+                torch.nn.functional.pad(wins, pad, value=-1))
+    return vals[:, :k].contiguous(), recs[:, :k].contiguous(), wins[:, :k].contiguous()
 
 
 class RowBank:
@@ -366,6 +443,12 @@ class AudioStateStore:
     mean, as bf16, for either.  Both sets of rows are RowBanks, kv_bank and align_bank; kv / kv_scales
     and akv / akv_scales are their tensors.
 
+    add_recording appends one long recording: its frames' rows once, and one entry per
+    overlapping window, a view of those rows (so entries may share rows, len() counts windows, and rows /
+    nbytes count each frame once; nbytes does not count the 8 bytes per entry of recording_of /
+    offset_of).  recording_of / offset_of say which recording an entry belongs to and where in it it
+    starts; a clip of add() is a recording of its own at offset 0.
+
     The store is valid for the weights it was built with: it records the model's
     ParamStore.weights_token() at the first add, and adding to or scoring against it after the
     weights changed raises RuntimeError (check)."""
@@ -390,6 +473,11 @@ class AudioStateStore:
         self._aproj: list[torch.Tensor] = []
         self._dev = None                      # (seg_row int64 [N], frames int32 [N], aproj [N, P]) on the device
         self._token = None
+        # add_recording: an entry is a window of a recording; a clip of add() is a recording of its own
+        self._rec_of: list[int] = []
+        self._off_of: list[int] = []
+        self._rec_dev = None                  # (recording_of int32 [N], offset_of int32 [N]) on the device
+        self.recordings = 0
 
     def __len__(self) -> int:
         return len(self._seg_len)
@@ -467,12 +555,113 @@ class AudioStateStore:
             self._seg_row.append(self.rows)
             self._seg_len.append(n)
             self.rows += n
+            self._rec_of.append(self.recordings)
+            self._off_of.append(0)
+            self.recordings += 1
         aproj = aproj.detach().float()
         self._aproj.append(aproj.clone())
         self.index.add(_unit_rows(aproj))
-        self._dev = None
+        self._dev = self._rec_dev = None
         if self._token is None:
             self._token = model.store.weights_token()
+
+    @torch.no_grad()
+    def add_recording(self, input_values, *, window_frames: int = 1500, hop_frames: int = 750,
+                      chunk_frames: int = 1000, context_frames: int = 250, chunk_batch: int = 8) -> int:
+        """Append ONE long recording and return its recording id.  input_values: its w2v-bert
+        features [F, 160] (or [1, F, 160]), every frame valid.  plan_recording says how: the encoder runs
+        chunk by chunk (engine.audio_forward in eval arithmetic on batches of chunk_batch chunk inputs,
+        right-padded under a prefix mask; each chunk keeps its own frames and drops the context), the
+        K|V rows and the alignment rows of the F kept frames are appended ONCE, back to back, and every
+        window becomes one ordinary entry of the store: a VIEW of those rows (seg_row = the recording's
+        first row + the window's start, frames = its length), with its own aproj and unit row, pooled
+        from the recording's hidden states in place by ops.attn_pool_seg_fwd.  So len(store) counts
+        windows, rows and nbytes count each frame once, and search, score_clips, rerank_clips, locate_clips,
+        kv_rows(n) and align_kv_rows(n) take window ids unchanged; recording_of / offset_of map a window
+        back (retrieval.search_recordings).  The defaults make the largest encoder input 1500 frames.
+
+        ValueError, before anything is appended: a raw-waveform (wav2vec2) model, a model without
+        use_attentive_pooling, plan_recording's refusals, window_frames over 2048 with align_rows.
+        RuntimeError if the weights changed (check)."""
+        model, eng = self.model, self.model.engine
+        if eng.raw_audio:
+            raise ValueError("add_recording takes w2v-bert features; a raw-waveform (wav2vec2) model is not supported")
+        if not model.use_attentive_pooling:
+            raise ValueError("add_recording needs a model built with use_attentive_pooling=True")
+        x = input_values
+        if x.dim() == 3 and x.shape[0] == 1:
+            x = x[0]
+        if x.dim() != 2:
+            raise ValueError(f"add_recording takes the features [F, 160] of ONE recording, got {tuple(input_values.shape)}")
+        if int(chunk_batch) < 1:
+            raise ValueError(f"chunk_batch must be at least 1, got {chunk_batch}")
+        F, fin = x.shape
+        plan = plan_recording(F, window_frames, hop_frames, chunk_frames, context_frames,
+                              max_window=ALIGN_MAX_FRAMES if self.align_rows else POOL_MAX_FRAMES)
+        self.check()
+        model.store.sync_shadow()
+        x = x.to(self.device).contiguous()
+        D = eng.acfg.hidden_size
+        h = torch.empty(F, D, device=self.device, dtype=F32)          # the kept frames' states
+        hs = torch.empty(F, 2 * D, device=self.device, dtype=BF16)    # and their [hi | lo] split image
+        chunks = list(zip(plan["keep"], plan["input"]))
+        for c0 in range(0, len(chunks), int(chunk_batch)):
+            part = chunks[c0:c0 + int(chunk_batch)]
+            T = max(ib - ia for _, (ia, ib) in part)
+            feats = x.new_zeros(len(part), T, fin)
+            mask = torch.zeros(len(part), T, dtype=torch.int64, device=self.device)
+            for j, (_, (ia, ib)) in enumerate(part):
+                feats[j, :ib - ia] = x[ia:ib]
+                mask[j, :ib - ia] = 1
+            ctx = {}
+            hc, _ = eng.audio_forward(feats, mask, False, 0, ctx, save=False)
+            for j, ((ka, kb), (ia, _)) in enumerate(part):
+                r = j * T + ka - ia
+                h[ka:kb] = hc[r:r + kb - ka]
+                hs[ka:kb] = ctx["a_hs"][r:r + kb - ka]
+        base = self.rows
+        if self.fused or self.align_rows:
+            hb = ops.cast_bf16(h, torch.empty(F, D, device=self.device, dtype=BF16))
+            self._reserve(base + F)
+            if self.fused:
+                self.kv_bank.write(base, eng._kv("text_to_audio_attention", "audio_seq_to_projection", hb)[0], [F], F)
+            if self.align_rows:
+                from .align import audio_kv
+                self.align_bank.write(base, audio_kv(eng, hb), [F], F)
+        starts, lens = plan["window_start"], plan["window_len"]
+        pooled = eng._pool_seg_fwd("audio_pooling", h, hs, torch.tensor(starts, dtype=torch.int64, device=self.device),
+                                   torch.tensor(lens, dtype=I32, device=self.device))
+        aproj = eng._proj_fwd("audio_projection", pooled, len(starts), False, 0, {})
+        rec = self.recordings
+        for s, n in zip(starts, lens):
+            self._seg_row.append(base + s)
+            self._seg_len.append(n)
+            self._rec_of.append(rec)
+            self._off_of.append(s)
+        self.rows += F
+        self.recordings += 1
+        self._aproj.append(aproj.clone())
+        self.index.add(_unit_rows(aproj))
+        self._dev = self._rec_dev = None
+        if self._token is None:
+            self._token = model.store.weights_token()
+        return rec
+
+    def _rec_tables(self):
+        if self._rec_dev is None:
+            self._rec_dev = (torch.tensor(self._rec_of, dtype=I32, device=self.device),
+                             torch.tensor(self._off_of, dtype=I32, device=self.device))
+        return self._rec_dev
+
+    @property
+    def recording_of(self) -> torch.Tensor:
+        """int32 [N]: the recording each entry (window) belongs to; a clip of add() is a recording of its own."""
+        return self._rec_tables()[0]
+
+    @property
+    def offset_of(self) -> torch.Tensor:
+        """int32 [N]: the entry's first frame inside its recording (0 for a clip of add())."""
+        return self._rec_tables()[1]
 
     def _tables(self):
         if self._dev is None:
@@ -554,6 +743,73 @@ def search_clips(model, store, input_ids, attention_mask, k, *, rerank=True, loc
     where = model.locate_clips(input_ids, attention_mask, store, idx, word_ids=word_ids, text_encoded=enc,
                                free_ends=free_ends, spot_bias=spot_bias) if locate else None
     return vals, idx, where
+
+
+def _same_recording(store, win, other):
+    """other where it is a window of win's recording, else -1 (win, other int [Q, k]; -1 = none)."""
+    N = len(store)
+    ok = (win >= 0) & (other >= 0) & (other < N)
+    rec = store.recording_of
+    ok = ok & (rec[win.clamp(min=0).long()] == rec[other.clamp(0, max(N - 1, 0)).long()])
+    return torch.where(ok, other, torch.full_like(other, -1))
+
+
+@torch.no_grad()
+def search_recordings(model, store, input_ids, attention_mask, k, *, window_k=None, rerank=True, locate=True,
+                      neighbours=True, free_ends=True, spot_bias=0.0, word_ids=None):
+    """A typed phrase against an archive of long recordings (AudioStateStore.add_recording):
+    search_clips over the store's windows, reduced to one hit per recording and reported in recording
+    time.  ONE text-encoder pass per query, shared by every stage.  Stage 1 searches m = window_k or
+    min(4·k, 128, len(store)) windows (128: the top-k kernel's limit); with rerank=True and a
+    use_cross_modal model rerank_clips reorders them; best_per_recording keeps each recording's best
+    window.  Returns (values fp32 [Q, k], recordings [Q, k], windows [Q, k], location), empty slots
+    (-inf, -1, -1); location is None with locate=False.
+
+    locate=True (needs a store built with align_rows=True) runs model.locate_clips on the chosen windows
+    (free_ends / spot_bias as in search_clips; the default here is the free-endpoint decode, since a
+    window rarely holds exactly the phrase).  neighbours=True (with free_ends=True only) also locates
+    the previous and the next window OF THE SAME RECORDING, in one locate_clips call on [Q, 3k]
+    candidates (centre | previous | next, -1 where there is none), and keeps per hit the window with the
+    largest path_score, the first maximum in that order winning; `windows` reports the window kept.
+    location is locate_clips' dict for the kept windows plus recording_hit_spans / recording_hit_seconds
+    and recording_token_spans / recording_token_seconds: the window-local values moved by the window's
+    offset_of (times engine.frame_seconds), (-1, -1) kept."""
+    if attention_mask is None:
+        attention_mask = torch.ones_like(input_ids)
+    k = int(k)
+    m = int(window_k) if window_k else min(4 * k, 128, len(store))
+    with model._eval_arithmetic():
+        enc = model.encode_text(input_ids, attention_mask)
+    vals, idx = store.search(_unit_rows(enc[0]), max(m, 1))
+    if rerank and getattr(model, "use_cross_modal", False):
+        vals, idx = rerank_clips(model, input_ids, attention_mask, store, idx, text_encoded=enc)
+    vals, recs, wins = best_per_recording(vals, idx, store.recording_of, k)
+    if not locate:
+        return vals, recs, wins, None
+    kw = dict(word_ids=word_ids, text_encoded=enc, free_ends=free_ends, spot_bias=spot_bias)
+    if neighbours and free_ends:
+        cand = torch.cat([wins, _same_recording(store, wins, wins - 1), _same_recording(store, wins, wins + 1)], 1)
+        where3 = model.locate_clips(input_ids, attention_mask, store, cand, **kw)
+        Q = wins.shape[0]
+        pc, pl, pr = where3["path_score"].view(Q, 3, k).unbind(1)
+        sel = (pl > pc).long()                                       # centre, unless the previous window beats it,
+        sel = torch.where(pr > torch.maximum(pc, pl), 2, sel)        # unless the next one beats both
+        wins = cand.view(Q, 3, k).gather(1, sel.view(Q, 1, k).to(cand.device)).squeeze(1)
+        where = {}
+        for key, v in where3.items():
+            v = v.view(Q, 3, k, *v.shape[2:])
+            pick = sel.view(Q, 1, k, *([1] * (v.dim() - 3))).expand(Q, 1, k, *v.shape[3:])
+            where[key] = v.gather(1, pick).squeeze(1)
+    else:
+        where = model.locate_clips(input_ids, attention_mask, store, wins, **kw)
+    off = torch.where(wins >= 0, store.offset_of[wins.clamp(min=0).long()], 0).to(I32)
+    fs = model.engine.frame_seconds
+    for name, o in (("hit", off.view(*off.shape, 1)), ("token", off.view(*off.shape, 1, 1))):
+        spans = where[name + "_spans"]
+        where[f"recording_{name}_spans"] = torch.where(spans < 0, spans, spans + o)
+        secs = where[name + "_seconds"]
+        where[f"recording_{name}_seconds"] = torch.where(spans < 0, secs, secs + o.float() * fs)
+    return vals, recs, wins, where
 
 
 def _pad_rows(chunks, fill):

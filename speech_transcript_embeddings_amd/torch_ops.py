@@ -38,6 +38,8 @@ through them); the fused training step itself calls the C ABI directly (engine.p
         monotone (Viterbi) decode of that log matrix into one frame span per token
     ste::align_spot(emit, ntok, nfrm, bg, lead=0) -> (spans, hit, score)
         the same decode with both ends free against a per-pair background: phrase spotting
+    ste::attn_pool_seg(t, w2, b2, h, seg_row, seg_len) -> pooled
+        AttentivePooling (ref :171-211) of overlapping segments of one row buffer: a recording's windows
 
 Every op fails loudly (SteError) without the HIP library; there is no CPU implementation.
 """
@@ -475,6 +477,21 @@ def _align_spot_fake(emit, ntok, nfrm, bg, lead=0):
             emit.new_empty(B, dtype=F32))
 
 
+@torch.library.custom_op("ste::attn_pool_seg", mutates_args=())
+def attn_pool_seg(t: Tensor, w2: Tensor, b2: Tensor, h: Tensor, seg_row: Tensor, seg_len: Tensor) -> Tensor:
+    """AttentivePooling (ref :171-211, after its first Linear + tanh) of G segments of one row buffer
+    (DESIGN §23): t [rows, Hh], h [rows, H], both fp32 or both bf16; segment g is rows seg_row[g] ..
+    seg_row[g] + seg_len[g] - 1, overlapping freely -> pooled fp32 [G, H], each row the bits of the dense
+    pooling of a copy of its rows.  Forward only."""
+    return ops.attn_pool_seg_fwd(t.contiguous(), w2.float().reshape(-1).contiguous(), b2.float().reshape(-1).contiguous(),
+                                 h.contiguous(), seg_row.reshape(-1).to(torch.int64).contiguous(), _i32(seg_len))
+
+
+@attn_pool_seg.register_fake
+def _attn_pool_seg_fake(t, w2, b2, h, seg_row, seg_len):
+    return h.new_empty(seg_len.numel(), h.shape[1], dtype=F32)
+
+
 OPS = ("fbank", "linear", "layer_norm", "attention", "pair_loss", "adamw_", "resample", "topk_sim", "xattn_mq",
        "xattn_seg", "xattn_seg_mx8", "align_matrix", "align_matrix_seg", "align_matrix_seg_mx8", "align_decode",
-       "align_spot")
+       "align_spot", "attn_pool_seg")
